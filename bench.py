@@ -10,6 +10,12 @@ generate_data.py-style blobs (seeded, synthetic). N > 1 splits the same problem 
 Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 under torch.distributed.run
 (one process per GPU, RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from the environment).
 Rank 0 prints exactly one JSON line on stdout; diagnostics go to stderr.
+
+A plain run does what the headline figure needs and no more: set-up, warm-up, the K timed iterations, the result
+line. --full adds everything else the benchmark measures, each in runs of its own: the K·p / dominant-kernel timing
+and the roofline built on it, the committed PMC figures, the oracle's CPU baseline, the time to solution (learn) and
+the other BASELINE rows. --dump-outputs DIR writes what the timed iterations computed (x and the residual trace) as
+DIR/<name>.npy, so that two builds can be compared output for output on the same seeded problem.
 """
 import argparse
 import json
@@ -101,11 +107,14 @@ def collective_desc(world, sim, exchange):
 
 
 def run_config(name, args, rank, world, dist, uid, steps, warmup, want_cpu, cpu_seconds, kp_reps, sim=None,
-               kernel=None, dtype=None, points=0, features=0, data_cache=None, solve=False, solve_cap_s=20.0):
+               kernel=None, dtype=None, points=0, features=0, data_cache=None, solve=False, solve_cap_s=20.0,
+               full=True, dump_dir=None):
     """Measure one BASELINE configuration: setup, q, r0, `warmup` + `steps` CG iterations (timed with
-    a barrier and stream synchronisation on both sides, max over ranks), the dominant kernel's
-    average launch time (hipEvents on the engine stream), roofline, committed PMC traffic and the
-    oracle's CPU baseline. Returns the record (bench-line keys) without the metric header."""
+    a barrier and stream synchronisation on both sides, max over ranks); with `full` also the dominant
+    kernel's average launch time (hipEvents on the engine stream), roofline and committed PMC traffic,
+    with `want_cpu` the oracle's CPU baseline, with `solve` the time to solution. `dump_dir`: rank 0 writes
+    the state the timed iterations left (dump_outputs). Returns the record (bench-line keys) without the
+    metric header."""
     cfg = CONFIGS[name]
     if kernel:
         cfg = (kernel,) + tuple(cfg[1:])
@@ -144,8 +153,15 @@ def run_config(name, args, rank, world, dist, uid, steps, warmup, want_cpu, cpu_
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dump_dir:
+        # every rank: a sharded group gathers the rows of x
+        x, trace, _ = svm.cg_result(min(warmup + steps + 1, 4096))
+        if rank == 0:
+            dump_outputs(dump_dir, x, trace)
     info = svm.info()
-    ms_kp, ms_dom = svm.time_kp(kp_reps)
+    ms_kp = ms_dom = None
+    if full:
+        ms_kp, ms_dom = svm.time_kp(kp_reps)
     learn = None
     if solve:
         # time to solution (csvm.cpp:226-266 reports setup and CG separately): the reference's learn() —
@@ -172,8 +188,23 @@ def run_config(name, args, rank, world, dist, uid, steps, warmup, want_cpu, cpu_
         log(f"[rank {rank}] {name}: learn at eps 1e-3: setup {t_setup:.2f}s + q {t_q:.3f}s + CG {it} iterations "
             f"{t_cg:.3f}s (converged: {conv})")
     svm.close()
-    roof = roofline(cfg, info, n, d, share, ms_dom, extra, ms_kp)
     dts = "f64" if dt == np.float64 else "f32"
+    rec = {
+        "value": steps / elapsed, "unit": "CG iterations/s", "ms_per_step": elapsed / steps * 1e3, "steps": steps,
+        "warmup": warmup, "dtype": dts,
+        "config": {"workload": desc, "N": n, "d": d, "kernel": kern, "layout": layout,
+                   "kp_mode": {1: "pairwise", 2: "factored"}[info["kp_mode"]],
+                   "parallelism": collective_desc(world, sim, args.host_exchange), "setup_s": round(t_setup, 3)},
+    }
+    if info["is_sparse"]:
+        rec["config"]["nnz"] = info["nnz"]
+    if sim:
+        rec["config"]["simulated_rank"] = f"{sim[0]}/{sim[1]}"
+    if learn is not None:
+        rec["learn"] = learn
+    if not full:
+        return rec
+    roof = roofline(cfg, info, n, d, share, ms_dom, extra, ms_kp)
     tkey = name + (f"_sim{sim[0]}of{sim[1]}" if sim else "")
     hs = roof.get("h_storage")
     tag = None if hs is None else ("bf16" if hs.startswith("bfloat16") else "real") + \
@@ -190,23 +221,19 @@ def run_config(name, args, rank, world, dist, uid, steps, warmup, want_cpu, cpu_
         cpu = cpu_baseline(kern, dt, d, n - 1, cpu_seconds, extra)
         if layout != "dense" and kern == "linear":
             cpu_fact = cpu_baseline_factored(dt, extra, cpu_seconds * 0.5)
-    rec = {
-        "value": steps / elapsed, "unit": "CG iterations/s", "ms_per_step": elapsed / steps * 1e3, "steps": steps,
-        "warmup": warmup, "dtype": dts,
-        "config": {"workload": desc, "N": n, "d": d, "kernel": kern, "layout": layout,
-                   "kp_mode": {1: "pairwise", 2: "factored"}[info["kp_mode"]],
-                   "parallelism": collective_desc(world, sim, args.host_exchange), "setup_s": round(t_setup, 3)},
-        "roofline": roof, "cpu_baseline": cpu, "kp_ms": ms_kp,
-    }
+    rec.update(roofline=roof, cpu_baseline=cpu, kp_ms=ms_kp)
     if cpu_fact is not None:
         rec["cpu_baseline_factored"] = cpu_fact
-    if learn is not None:
-        rec["learn"] = learn
-    if info["is_sparse"]:
-        rec["config"]["nnz"] = info["nnz"]
-    if sim:
-        rec["config"]["simulated_rank"] = f"{sim[0]}/{sim[1]}"
     return rec
+
+
+def dump_outputs(dump_dir, x, trace):
+    """What a caller of the timed path receives after its last iteration (cg_result): the iterate x in the
+    configuration's real type and the residual trace r^T r (float64: before iteration 0, then after every
+    iteration, warm-up included). The problem is seeded, so equal arguments give equal inputs."""
+    os.makedirs(dump_dir, exist_ok=True)
+    np.save(os.path.join(dump_dir, "x.npy"), x)
+    np.save(os.path.join(dump_dir, "residual_trace.npy"), trace)
 
 
 def main():
@@ -221,6 +248,12 @@ def main():
                     help="override the configuration's kernel function (ablations)")
     ap.add_argument("--dtype", choices=["f32", "f64"], default=None,
                     help="override the configuration's real type (parity/throughput studies, not the headline line)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: K·p / dominant-kernel timing and roofline, "
+                         "committed PMC figures, the CPU baseline, the default line's learn() timing and the other "
+                         "BASELINE rows (each can be switched off: --no-cpu, --no-solve, --no-extra)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what they computed (x, residual_trace) as DIR/<name>.npy")
     ap.add_argument("--kp-reps", type=int, default=3)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-extra", action="store_true",
@@ -272,12 +305,13 @@ def main():
     default_cfg = args.config == "dense_rbf_100k" and not (args.kernel or args.dtype or args.points or args.features
                                                           or sim)
     default_run = default_cfg and world == 1
-    rec = run_config(args.config, args, rank, world, dist, uid, args.steps, args.warmup, not args.no_cpu,
+    rec = run_config(args.config, args, rank, world, dist, uid, args.steps, args.warmup, args.full and not args.no_cpu,
                      args.cpu_seconds, args.kp_reps, sim=sim, kernel=args.kernel, dtype=args.dtype,
                      points=args.points, features=args.features, data_cache=cache,
-                     solve=(args.solve or default_run) and not args.no_solve and world == 1)
+                     solve=(args.solve or (default_run and args.full)) and not args.no_solve and world == 1,
+                     full=args.full, dump_dir=args.dump_outputs)
     extra = None
-    if default_cfg and not args.no_extra:
+    if args.full and default_cfg and not args.no_extra:
         # the other BASELINE rows measured under the same clock. One GPU: configs[2] with RBF (the >= 70 % HBM
         # row), configs[2] itself (sparse linear, same seeded matrix), configs[4] (2M x 100k FP22 RBF, on one
         # GPU: the kernel expansion's memory is O(nnz + multi-feature pairs)) and configs[3] (dense linear
@@ -315,11 +349,8 @@ def main():
             "dtype": rec["dtype"],
             "data": "synthetic (seeded generate_data.py-style blobs / sparse CSR)",
             "config": rec["config"],
-            "roofline": rec["roofline"],
-            "cpu_baseline": rec["cpu_baseline"],
-            "kp_ms": rec["kp_ms"],
         }
-        for k in ("cpu_baseline_factored", "learn"):
+        for k in ("roofline", "cpu_baseline", "kp_ms", "cpu_baseline_factored", "learn"):
             if k in rec:
                 out[k] = rec[k]
         if extra:

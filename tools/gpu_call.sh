@@ -8,7 +8,7 @@ timeout -k 10 900 python -u -m pytest -q --timeout 300 --timeout-method thread -
 rc=$?; echo "pytest rc=$rc"; tail -3 "$out/pytest.log"
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1 || exit $?
-timeout -k 10 240 python bench.py > "$out/bench.json" 2> "$out/bench.err"; echo "bench rc=$?"
+timeout -k 10 240 python bench.py --full > "$out/bench.json" 2> "$out/bench.err"; echo "bench rc=$?"
 python3 - "$out/bench.json" <<'PY'
 import json, sys
 b = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

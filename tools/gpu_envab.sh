@@ -8,6 +8,6 @@ for rep in 1 2; do
   i=0
   for e in "" "$@"; do
     i=$((i+1))
-    env $e timeout -k 10 300 python bench.py --config $cfg --no-cpu --steps $steps --warmup 2 > $out/${cfg}_${i}_$rep.json 2> $out/${cfg}_${i}_$rep.err
+    env $e timeout -k 10 300 python bench.py --full --config $cfg --no-cpu --steps $steps --warmup 2 > $out/${cfg}_${i}_$rep.json 2> $out/${cfg}_${i}_$rep.err
   done
 done

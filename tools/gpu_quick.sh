@@ -8,7 +8,7 @@ mkdir -p "$out"
 timeout -k 10 600 python -u -m pytest -x -v --timeout 300 --timeout-method thread -m gpu "$@" > "$out/pytest.log" 2>&1
 rc=$?; echo "pytest rc=$rc"; tail -5 "$out/pytest.log"
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
-timeout -k 10 400 python bench.py > "$out/bench.json" 2> "$out/bench.err"; brc=$?; echo "bench rc=$brc"
+timeout -k 10 400 python bench.py --full > "$out/bench.json" 2> "$out/bench.err"; brc=$?; echo "bench rc=$brc"
 [ $brc -eq 0 ] || exit $brc
 python3 - "$out/bench.json" <<'PY'
 import json, sys

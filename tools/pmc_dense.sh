@@ -11,7 +11,7 @@ mkdir -p "$out"
 export TMPDIR=/tmp
 cd /tmp
 timeout -s KILL 180 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_VALU_MFMA_COEXEC_CYCLES SQ_INSTS_VALU \
-  --output-format csv -d "$out" -o run -- python3 "$root/bench.py" --steps 1 --warmup 0 --kp-reps 1 --no-cpu --no-extra --no-solve "$@" > "$out/bench.json" 2> "$out/bench.log"
+  --output-format csv -d "$out" -o run -- python3 "$root/bench.py" --full --steps 1 --warmup 0 --kp-reps 1 --no-cpu --no-extra --no-solve "$@" > "$out/bench.json" 2> "$out/bench.log"
 python3 - "$out" "$*" <<'PY'
 import csv, sys, collections, glob, json
 out, args = sys.argv[1], sys.argv[2]

@@ -9,7 +9,7 @@ mkdir -p "$out"
 export TMPDIR=/tmp
 cd /tmp
 timeout -s KILL 240 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CU_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VALU SQ_LDS_BANK_CONFLICT \
-  --output-format csv -d "$out" -o run -- python3 "$root/bench.py" --config "$config" --steps 1 --warmup 0 --kp-reps 1 --no-cpu --no-extra --no-solve > "$out/bench.json" 2> "$out/bench.log"
+  --output-format csv -d "$out" -o run -- python3 "$root/bench.py" --full --config "$config" --steps 1 --warmup 0 --kp-reps 1 --no-cpu --no-extra --no-solve > "$out/bench.json" 2> "$out/bench.log"
 python3 - "$out" <<'PY'
 import csv, sys, collections, glob, json
 out = sys.argv[1]

@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 for rows in pairs flags; do
   cd /tmp
   PLSSVM_MI_EXP_ROWS=$rows timeout -s KILL 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_INST_ANY SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VALU SQ_WAIT_INST_LDS \
-    --output-format csv -d "$out/$rows" -o run -- python3 "$root/bench.py" --config fp22_rbf_2m --steps 2 --warmup 0 --kp-reps 1 --no-cpu --no-extra --no-solve > "$out/$rows.bench.json" 2> "$out/$rows.log" || exit $?
+    --output-format csv -d "$out/$rows" -o run -- python3 "$root/bench.py" --full --config fp22_rbf_2m --steps 2 --warmup 0 --kp-reps 1 --no-cpu --no-extra --no-solve > "$out/$rows.bench.json" 2> "$out/$rows.log" || exit $?
   cd "$root"
   python3 - "$out" "$rows" <<'PY'
 import csv, sys, collections, glob, json

@@ -9,7 +9,7 @@ mkdir -p "$out"
 export TMPDIR=/tmp
 cd /tmp
 timeout -s KILL 240 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$out" -o run -- \
-  python3 "$root/bench.py" --config "$config" --steps 2 --warmup 0 --kp-reps 1 --no-cpu --no-extra --no-solve "$@" \
+  python3 "$root/bench.py" --full --config "$config" --steps 2 --warmup 0 --kp-reps 1 --no-cpu --no-extra --no-solve "$@" \
   > "$out/bench.json" 2> "$out/bench.log"
 python3 - "$out" <<'PY'
 import csv, sys, collections, glob, json

@@ -9,6 +9,6 @@ mkdir -p "$out"
 export TMPDIR=/tmp
 cd /tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o run -- \
-  python3 "$root/bench.py" --no-cpu "$@" > "$out/bench.json" 2> "$out/bench.err"
+  python3 "$root/bench.py" --full --no-cpu "$@" > "$out/bench.json" 2> "$out/bench.err"
 find "$out" -type f ! -name '*kernel_stats.csv' ! -name '*.json' ! -name '*.err' -delete
 echo "stats $tag done"

@@ -7,7 +7,7 @@ config=$1; W=$2; shift 2
 out=gpurun_out/shares_${config}_${W}.jsonl
 : > "$out"
 for r in $(seq 0 $((W - 1))); do
-  timeout -k 10 300 python bench.py --config "$config" --sim-rank "$r/$W" --steps 5 --warmup 1 --no-cpu "$@" 2>/dev/null >> "$out"
+  timeout -k 10 300 python bench.py --full --config "$config" --sim-rank "$r/$W" --steps 5 --warmup 1 --no-cpu "$@" 2>/dev/null >> "$out"
 done
 python3 - "$out" <<'PY'
 import json, sys
