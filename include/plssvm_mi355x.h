@@ -106,6 +106,13 @@ extern "C" {
 #define PLSSVM_MI_CG_ONE_REDUCTION 1
 #define PLSSVM_MI_CG_AUTO 2
 
+/* Stored kernel-matrix tiles of the dense pairwise path (also sparse data densified on the device): the first K·p of
+ * a setup stores the 128 x 128 tiles of k(x_i, x_j) it forms, as many as the device memory budget holds (85 % of the
+ * free memory, PLSSVM_MI_MEM_BUDGET = bytes overrides it), every later K·p streams them from HBM instead of
+ * recomputing them; tiles that do not fit stay implicit. The results are bitwise those of the implicit product.
+ *   0 = auto (on where it fits), 1 = off. Environment PLSSVM_MI_KP_CACHE=0, read at setup, also turns it off. */
+#define PLSSVM_MI_OPT_KP_CACHE 6
+
 typedef struct plssvm_mi_ctx plssvm_mi_ctx;
 
 /* Number of visible HIP devices (>= 0), or a negative error code. */
@@ -294,6 +301,9 @@ typedef struct {
                            (engine.hpp ctr_*; PLSSVM_MI_CTR=0 or a caller's own q vector: 0) */
     int exp_lt;         /* kernel expansion: 1 = the remainder's rows came from the lower-triangle join + transpose
                            (one rank holding every row; PLSSVM_MI_EXP_LT=0: the full join) */
+    int64_t kp_cache_tiles; /* pairwise tile path: tiles of this rank whose kernel values are kept in HBM
+                               (PLSSVM_MI_OPT_KP_CACHE); tiles_local when all fit, 0 = none */
+    int64_t kp_cache_bytes; /* device bytes of those records (tile_rows x tile_cols reals each) */
 } plssvm_mi_info;
 PLSSVM_MI_API int plssvm_mi_get_info(const plssvm_mi_ctx *ctx, plssvm_mi_info *info);
 

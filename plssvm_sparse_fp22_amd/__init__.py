@@ -158,7 +158,7 @@ class CSVM:
     """One MI355X context (one GPU, one HIP stream). ``world_size > 1`` joins a row-block group."""
 
     def __init__(self, params: Parameter, device=0, rank=0, world_size=1, uid=None, kp_mode="auto",
-                 sim_rank=None, rbf_form=0, exchange=None, sparse_algo="auto", cg_variant=None):
+                 sim_rank=None, rbf_form=0, exchange=None, sparse_algo="auto", cg_variant=None, kp_cache=None):
         if params.data is None and params.csr is None and params.coo is None:
             raise ValueError("No data points provided!")
         if params.data is not None:
@@ -187,6 +187,8 @@ class CSVM:
         if cg_variant is not None:  # "reference" | "one_reduction" | "auto", see PLSSVM_MI_OPT_CG_VARIANT
             v = {"reference": 0, "one_reduction": 1, "auto": 2}[cg_variant]
             self._check(L.plssvm_mi_set_option(self._ctx, _abi.OPT_CG_VARIANT, v))
+        if kp_cache is not None:  # False: never store kernel-matrix tiles, see PLSSVM_MI_OPT_KP_CACHE
+            self._check(L.plssvm_mi_set_option(self._ctx, _abi.OPT_KP_CACHE, 0 if kp_cache else 1))
         if sim_rank is not None:  # (rank, world): single-GPU test hook, see PLSSVM_MI_OPT_SIM_RANK
             self._check(L.plssvm_mi_set_option(self._ctx, _abi.OPT_SIM_RANK, sim_rank[0] | (sim_rank[1] << 16)))
         if exchange is not None:  # host-staged group: fn(numpy buffer, op) combines in place (torch_exchange)

@@ -37,6 +37,7 @@ OPT_SIM_RANK = 2
 OPT_RBF_FORM = 3
 OPT_SPARSE_ALGO = 4
 OPT_CG_VARIANT = 5
+OPT_KP_CACHE = 6
 SPARSE_AUTO, SPARSE_PATTERN, SPARSE_EXPANSION, SPARSE_DENSE, SPARSE_ONTHEFLY = 0, 1, 2, 3, 4
 PART_KERNEL, PART_OVERLAP, PART_REMAINDER = 0, 1, 2
 XCHG_ALLREDUCE, XCHG_ALLGATHER = 0, 1
@@ -56,7 +57,7 @@ class Info(ctypes.Structure):
                [("rbf_small_args", ctypes.c_int), ("sparse_algo", ctypes.c_int), ("exp_terms", ctypes.c_int),
                 ("exp_waves", ctypes.c_int), ("exp_chunks", ctypes.c_int64), ("exp_hbytes", ctypes.c_int),
                 ("exp_layout", ctypes.c_int), ("exp_dot2", ctypes.c_int), ("centered", ctypes.c_int),
-                ("exp_lt", ctypes.c_int)]
+                ("exp_lt", ctypes.c_int), ("kp_cache_tiles", ctypes.c_int64), ("kp_cache_bytes", ctypes.c_int64)]
 
 
 class BackendError(RuntimeError):

@@ -113,6 +113,8 @@ int plssvm_mi_set_option(plssvm_mi_ctx *ctx, int key, int64_t value) {
             e.sparse_algo = (int) value;
         } else if (key == PLSSVM_MI_OPT_CG_VARIANT && value >= 0 && value <= 2) {
             e.cg_variant = (int) value;
+        } else if (key == PLSSVM_MI_OPT_KP_CACHE && value >= 0 && value <= 1) {
+            e.kp_cache_opt = (int) value;
         } else {
             throw mi_error(PLSSVM_MI_ERR_ARG, "bad option");
         }
@@ -406,6 +408,8 @@ int plssvm_mi_get_info(const plssvm_mi_ctx *cctx, plssvm_mi_info *info) {
         info->exp_dot2 = e.csr.ex.on && e.csr.ex.hbf16 && e.csr.ex.dot2 && sizeof(e.gamma) == 4 && plssvm_mi::exp_dot2_built() ? 1 : 0;
         info->centered = e.ctr_active() ? 1 : 0;
         info->exp_lt = e.csr.ex.on && e.csr.ex.lt ? 1 : 0;
+        info->kp_cache_tiles = e.kcache_tiles;
+        info->kp_cache_bytes = e.kcache.bytes();
     });
 }
 

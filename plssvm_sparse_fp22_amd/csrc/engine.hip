@@ -105,6 +105,7 @@ engine<T>::~engine() {
     if (blas) (void) rocblas_destroy_handle(blas);
     XT.reset();
     partial.reset();
+    kcache.reset();
     if (stream) (void) hipStreamDestroy(stream);
 }
 
@@ -402,6 +403,7 @@ void engine<T>::finish_setup() {
     raw.alloc(vec_len, stream);
     w.alloc(std::max<int64_t>(d_pad, 1), stream);
     MI_HIP_CHECK(hipStreamSynchronize(stream));
+    kcache_setup();
     have_data = true;
     have_q = false;
     q_gen = false;
@@ -419,6 +421,49 @@ void engine<T>::tiles_upload() {
     kp_wgoff.alloc((int64_t) off.size(), stream, false);
     MI_HIP_CHECK(hipMemcpyAsync(kp_wgoff.get(), off.data(), sizeof(int32_t) * off.size(), hipMemcpyHostToDevice, stream));
     MI_HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+// The tile cache of this setup: as many of the rank's tiles as the memory budget holds, none for a path that does not
+// run the tile kernel. The records of an earlier setup are dropped first (their data is gone), nothing is written
+// here: the first K·p without a stop flag fills them (kp_tiles_now). No room, or an allocation that fails: no cache.
+template <typename T>
+void engine<T>::kcache_setup() {
+    kcache_valid = false;
+    kcache_tiles = 0;
+    kcache.reset();
+    const bool tiles_path = !factored() && (!sparse || csr.dense_on);  // kp_raw's launch_kp_tiles branch
+    const char *ke = std::getenv("PLSSVM_MI_KP_CACHE");
+    if (!tiles_path || kp_cache_opt == 1 || (ke != nullptr && std::atoi(ke) == 0) || kp_wgs <= 0 || m <= 0) return;
+    phase_timer pt;
+    const int64_t rec_bytes = KP_CACHE_REC * (int64_t) sizeof(T);
+    const int64_t tiles = std::min<int64_t>(kp_wgs, mem_budget() / rec_bytes);
+    if (tiles <= 0) return;
+    try {
+        kcache.alloc(tiles * KP_CACHE_REC, stream, false);
+    } catch (const mi_error &) {
+        (void) hipGetLastError();
+        kcache.reset();
+        return;
+    }
+    kcache_tiles = tiles;
+    pt.mark("kp cache alloc");
+}
+
+// The tile launches of one K·p. An unfilled cache is filled only by a K·p that no stop flag can cut short and that
+// is launched, not captured: a kernel leaving at `converged` must not leave records half written and trusted, and a
+// replayed graph must not store. Until then (and past the cached prefix) the tiles are computed.
+template <typename T>
+void engine<T>::kp_tiles_now(const T *p, const cg_scalars<T> *status) {
+    bool fill = false;
+    if (kcache_tiles > 0 && !kcache_valid && status == nullptr) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        MI_HIP_CHECK(hipStreamIsCapturing(stream, &cs));
+        fill = cs == hipStreamCaptureStatusNone;
+    }
+    const int64_t cached = (kcache_valid || fill) ? kcache_tiles : 0;
+    launch_kp_tiles<T>(kf(), XT.get(), norms.get(), p, partial.get(), n_pad, d_pad, nb, t0, t1 - t0, kp_wgoff.get(), kp_wgs,
+                       status, stream, kcache.get(), cached, fill);
+    if (fill) kcache_valid = true;
 }
 
 template <typename T>
@@ -489,8 +534,7 @@ void engine<T>::kp_raw(const T *p, const cg_scalars<T> *status) {
         if (!shard) allgather_rows(raw.get());
     } else {
         gather_input(p);
-        launch_kp_tiles<T>(kf(), XT.get(), norms.get(), p, partial.get(), n_pad, d_pad, nb, t0, t1 - t0, kp_wgoff.get(), kp_wgs, status,
-                           stream);
+        kp_tiles_now(p, status);
         launch_kp_reduce<T>(partial.get(), nb, m, t0, t1, kp_wgoff.get(), raw.get(), status, stream);
         if (shard) reduce_scatter_rows(raw.get());
         else allreduce(raw.get(), m);
@@ -908,7 +952,9 @@ void engine<T>::time_kp(int reps, double *ms_kp, double *ms_dom) {
     MI_HIP_CHECK(hipEventSynchronize(e1));
     float ms = 0;
     MI_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    // dominant kernel alone, same stream, same launches; before each launch a 512 MiB read sweep evicts what
+    // dominant kernel alone (the pairwise tiles: always the implicit kernel over all tiles, never the stored ones — the
+    // roofline built on this time is a statement about the MFMA kernel; ms_kp above is K·p as it runs, cache
+    // included), same stream, same launches; before each launch a 512 MiB read sweep evicts what
     // the previous launch left in the L2s and the Infinity Cache (256 MiB), as the other kernels of a CG
     // iteration do between two launches — back-to-back launches would otherwise re-read part of their stream
     // from there (a read, not a memset: dirty lines would be written back during the timed launch)
@@ -950,7 +996,8 @@ void engine<T>::time_kp(int reps, double *ms_kp, double *ms_dom) {
 
 template <typename T>
 int64_t engine<T>::device_bytes() const {
-    return XT.bytes() + norms.bytes() + xlast.bytes() + partial.bytes() + q.bytes() * 10 + w.bytes() + csr_bytes();
+    return XT.bytes() + norms.bytes() + xlast.bytes() + partial.bytes() + kcache.bytes() + q.bytes() * 10 + w.bytes() +
+           csr_bytes();
 }
 
 template struct engine<float>;

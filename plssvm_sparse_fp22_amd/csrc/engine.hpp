@@ -88,6 +88,17 @@ struct engine : engine_base {
     dev_buf<int32_t> kp_wgoff;  // tile kernel workgroup table (kp_tile_offsets), kp_wgs workgroups
     int64_t kp_wgs = 0;
     void tiles_upload();
+    // Stored kernel-matrix tiles of the pairwise tile path (kp_tiles.hip, KP_COMPUTE_STORE / KP_LOAD): the values
+    // k(x_i, x_j) depend only on the data and the kernel parameters, so the first K·p of a setup that runs without
+    // a stop flag (cg_begin's r0 product, kp_host) stores the first kcache_tiles tiles of this rank's table — all
+    // of them where mem_budget() allows — and every later K·p streams them instead of recomputing them; the tiles
+    // past the prefix stay implicit. kcache_valid: the records are written (by launches already on the stream).
+    int kp_cache_opt = 0;  // PLSSVM_MI_OPT_KP_CACHE: 0 auto (on where it fits), 1 off; env PLSSVM_MI_KP_CACHE=0: off
+    dev_buf<T> kcache;
+    int64_t kcache_tiles = 0;
+    bool kcache_valid = false;
+    void kcache_setup();  // after the setup's other allocations
+    void kp_tiles_now(const T *p, const cg_scalars<T> *status);  // the tile launches of one K·p
     int64_t r0 = 0, r1 = 0, chunk = 0;    // rows owned by this rank (factored / sparse row paths)
 
     // sharded CG (a real group on sparse data by default; PLSSVM_MI_SHARD = 0 / 1 overrides, 1 also for dense
@@ -213,7 +224,7 @@ struct engine : engine_base {
     // sparse paths (sparse.hip)
     void sparse_q();                                              // q, norms, e on CSR data
     void build_gram_blocks(const int64_t *cpos, int64_t max_inc);  // sparse Gram pattern (pairwise kernels)
-    int64_t sparse_mem_budget() const;                             // device bytes for stored sparse structures
+    int64_t mem_budget() const;  // device bytes for stored per-pair structures (sparse paths, dense tile cache)
     // row_stats (optional): the sampled rows' partners sharing >= 2 features, mean and max
     int64_t estimate_expansion_bytes(const int64_t *rowptr, const int32_t *col, const std::vector<int64_t> &colptr,
                                      const std::vector<int32_t> &crow, int64_t inc_total, double *row_stats = nullptr) const;

@@ -62,10 +62,18 @@ constexpr int KP_REC = 2 * KP_TILE;
 // wg_off[k] (k = 0..nsuper): first workgroup of super-block s0 + k (one workgroup per real tile: 64 for a
 // full super-block, 36 for a diagonal one, fewer in the ragged last row); wgs = wg_off[nsuper]
 void kp_tile_offsets(int64_t nb, int64_t s0, int64_t nsuper, std::vector<int32_t> &wg_off);
+// Modes of the tile kernel. The kernel values depend only on the data and the kernel parameters, so after the
+// first K·p of a setup they can come from HBM instead of the MFMAs: KP_COMPUTE_STORE writes tile wg's 128 x 128
+// values to kcache[wg][KP_CACHE_REC] (the lanes' register layout, kp_tiles.hip), KP_LOAD reads them back and
+// runs the same epilogue, giving bitwise the computed slab record.
+enum kp_tile_mode { KP_COMPUTE = 0, KP_COMPUTE_STORE = 1, KP_LOAD = 2 };
+constexpr int64_t KP_CACHE_REC = (int64_t) KP_TILE * KP_TILE;
+// tiles [0, cached) from / to kcache (fill: computed and stored, else loaded), tiles [cached, wgs) computed
 template <typename T>
 void launch_kp_tiles(kfun<T> kf, const T *XT, const T *norms, const T *p, T *partial, int64_t n_pad, int64_t d_pad,
                      int64_t nb, int64_t s0, int64_t nsuper, const int32_t *wg_off, int64_t wgs,
-                     const cg_scalars<T> *status, hipStream_t s);
+                     const cg_scalars<T> *status, hipStream_t s, T *kcache = nullptr, int64_t cached = 0,
+                     bool fill = false);
 
 // raw[i] = sum over the column blocks c in order of row i's slab values of the tiles whose super-block lies
 // in [s0, s1) (tile (Ib, c) row sums for c <= Ib, tile (c, Ib) column sums for c > Ib); i < m

@@ -157,15 +157,45 @@ constexpr bool kp_dma_after_reads() {
     return KP_DMA_AFTER_READS == 2 ? (sizeof(T) == 8 && KERNEL == 2) : KP_DMA_AFTER_READS == 1;
 }
 
-template <typename T, int KERNEL>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_waves_per_eu<T, KERNEL>(), kp_waves_per_eu<T, KERNEL>()))) void kp_tile_kernel(kfun<T> kf, const T *__restrict__ XT,
+// KP_LOAD streams a tile's stored kernel values instead of forming them: no K loop, LDS = the reduction buffers
+// only. Workgroups per CU (= waves per SIMD): KP_LOAD_WAVES, default 3 in fp64 (128 of <= 168 VGPRs hold the
+// tile's values: 3 x 128 KiB of loads in flight per CU) and 4 in fp32; A/B in DESIGN.md §3.1.2
+#ifndef KP_LOAD_WAVES
+#define KP_LOAD_WAVES 0
+#endif
+template <typename T, int KERNEL, int MODE>
+constexpr int kp_mode_waves() {
+    if (MODE != KP_LOAD) return kp_waves_per_eu<T, KERNEL>();
+    return KP_LOAD_WAVES > 0 ? KP_LOAD_WAVES : (sizeof(T) == 8 ? 3 : 4);
+}
+
+template <typename T>
+struct kp_vec;
+template <>
+struct kp_vec<double> {
+    typedef double type __attribute__((ext_vector_type(2)));
+};
+template <>
+struct kp_vec<float> {
+    typedef float type __attribute__((ext_vector_type(4)));
+};
+
+// MODE (kernels.hpp): KP_COMPUTE forms the tile's kernel values from the data; KP_COMPUTE_STORE also writes them
+// to the tile's cache record kcache[wg]; KP_LOAD reads them from there and runs the same epilogue from "times p_j"
+// on — the same fma order, LDS park and sums, so the slab record is bitwise the computed one. A cache record is
+// in register layout, [value group][thread][VEC]: a lane's 64 values in (mt, r, nt) order, 16 bytes per lane and
+// group, so every wave-instruction moves one contiguous KiB. wg_base: the first workgroup (tile) of this launch.
+template <typename T, int KERNEL, int MODE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_waves<T, KERNEL, MODE>(), kp_mode_waves<T, KERNEL, MODE>()))) void kp_tile_kernel(kfun<T> kf, const T *__restrict__ XT,
                                                          const T *__restrict__ norms, const T *__restrict__ p,
                                                          T *__restrict__ partial, int64_t n_pad, int64_t d_pad,
                                                          int64_t nb, int64_t s0, int64_t nsuper,
                                                          const int32_t *__restrict__ wg_off,
-                                                         const cg_scalars<T> *__restrict__ status) {
+                                                         const cg_scalars<T> *__restrict__ status, int64_t wg_base,
+                                                         T *__restrict__ kcache) {
     using M = mfma16<T>;
     using acc_t = typename M::acc_t;
+    using vec_t = typename kp_vec<T>::type;
     constexpr int BK = kp_bk<T, KERNEL>();
     constexpr int PANEL = BK * KP_TILE;            // elements of one [BK][128] panel
     constexpr int EPP = 1024 / (int) sizeof(T);    // elements per 1 KiB wave-instruction
@@ -177,9 +207,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_waves_pe
     constexpr int OFF_PAN = 4 * KP_TILE;
     constexpr int RSTR = 17, RHALF = KP_TILE * RSTR + 1, CSTR = 5;
     constexpr int RED = 2 * RHALF + 2 * KP_TILE * CSTR;
-    constexpr int SMEM = OFF_PAN + (4 * PANEL > RED ? 4 * PANEL : RED);
+    constexpr int SMEM = OFF_PAN + ((MODE != KP_LOAD && 4 * PANEL > RED) ? 4 * PANEL : RED);
     __shared__ __attribute__((aligned(16))) T smem[SMEM];
-    constexpr bool FAST_EXP = (KERNEL == 2) && sizeof(T) == 8;
+    constexpr bool FAST_EXP = (KERNEL == 2) && sizeof(T) == 8 && MODE != KP_LOAD;
+    constexpr int NGRP = 64 / VEC;  // 16-byte groups of a lane's 64 values
     __shared__ double exp_tab[FAST_EXP ? EXP_TAB : 1];
 
     if (status != nullptr && status->converged) return;
@@ -188,7 +219,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_waves_pe
     // super-block has 64 tiles, a diagonal one 36, the ragged last super-block row fewer): no empty
     // workgroups, so the XCDs' contiguous ranges carry equal work (empty ones bunched at the end of a
     // range made the last rank of 8 3.9 % slower than the others)
-    const int64_t wg = xcd_remap(blockIdx.x, gridDim.x);
+    // (KP_LOAD has no panels to keep in an L2: its workgroups walk the records in order)
+    const int64_t wg = wg_base + (MODE == KP_LOAD ? (int64_t) blockIdx.x : xcd_remap(blockIdx.x, gridDim.x));
     int lo = 0, hi = (int) nsuper;  // largest k with wg_off[k] <= wg
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
@@ -216,82 +248,92 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_waves_pe
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform, provably (scalar LDS bases)
     const int wr = w >> 1, wc = w & 1;
 
-    // p and norms of the tile's rows/cols -> LDS (issued first: their wait must not drain the DMA)
     const int64_t pidx = (tid < KP_TILE) ? I0 + tid : J0 + (tid - KP_TILE);
-    const T pin = p[pidx];
-    const T nin = (KERNEL == 2) ? norms[pidx] : T(0);
-    // fast fp64 RBF: the accumulators start at -n_j / 2 (column j = lane & 15 of every block), so they
-    // end at g_ij - n_j / 2 and y_ij = 2 g KEXP (g_ij - n_j / 2) - g KEXP n_i is one fma per element
-    T acc0[4];
+    acc_t acc[4][4];
+    vec_t kld[MODE == KP_LOAD ? NGRP : 1];
+    if constexpr (MODE == KP_LOAD) {
+        // all of the lane's loads are issued before the first use: the whole 128 KiB (fp64) record is in flight
+        const vec_t *rec = reinterpret_cast<const vec_t *>(kcache + wg * KP_CACHE_REC) + tid;
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-        acc0[nt] = FAST_EXP ? T(-0.5) * norms[J0 + wc * 64 + nt * 16 + (lane & 15)] : T(0);
+        for (int g = 0; g < NGRP; ++g) kld[g] = rec[g * 256];
+        smem[tid] = p[pidx];
+        __syncthreads();  // p_I, p_J visible
+    } else {
+        // p and norms of the tile's rows/cols -> LDS (issued first: their wait must not drain the DMA)
+        const T pin = p[pidx];
+        const T nin = (KERNEL == 2) ? norms[pidx] : T(0);
+        // fast fp64 RBF: the accumulators start at -n_j / 2 (column j = lane & 15 of every block), so they
+        // end at g_ij - n_j / 2 and y_ij = 2 g KEXP (g_ij - n_j / 2) - g KEXP n_i is one fma per element
+        T acc0[4];
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+            acc0[nt] = FAST_EXP ? T(-0.5) * norms[J0 + wc * 64 + nt * 16 + (lane & 15)] : T(0);
 
-    // per-lane byte offsets of this wave's DMA pieces inside a chunk (32-bit, reused for every chunk
-    // and both panels: the chunk base and the panel offset are wave-uniform, see glds16_buf)
-    uint32_t doff[PIECES];
-#pragma unroll
-    for (int j = 0; j < PIECES; ++j) {
-        const int elem = (w * PIECES + j) * EPP + lane * VEC;
-        doff[j] = (uint32_t) (((int64_t) (elem / KP_TILE) * n_pad + elem % KP_TILE) * (int64_t) sizeof(T));
-    }
-    // LDS-DMA through a buffer descriptor: the chunk base is a scalar pointer (SALU), the per-lane part
-    // is the constant doff and the panel offset goes in soffset — no VALU address math per chunk
-    const uint32_t offI = __builtin_amdgcn_readfirstlane((uint32_t) (I0 * (int64_t) sizeof(T)));
-    const uint32_t offJ = __builtin_amdgcn_readfirstlane((uint32_t) (J0 * (int64_t) sizeof(T)));
-    auto issue = [&](int64_t kc, int buf) {
-        const T *cb = XT + kc * BK * n_pad;
-        T *pa = smem + OFF_PAN + (2 * buf) * PANEL;
-        T *pb = pa + PANEL;
+        // per-lane byte offsets of this wave's DMA pieces inside a chunk (32-bit, reused for every chunk
+        // and both panels: the chunk base and the panel offset are wave-uniform, see glds16_buf)
+        uint32_t doff[PIECES];
 #pragma unroll
         for (int j = 0; j < PIECES; ++j) {
-            const int u = w * PIECES + j;
-            glds16_buf(cb, pa + u * EPP, doff[j], offI);
-            glds16_buf(cb, pb + u * EPP, doff[j], offJ);
+            const int elem = (w * PIECES + j) * EPP + lane * VEC;
+            doff[j] = (uint32_t) (((int64_t) (elem / KP_TILE) * n_pad + elem % KP_TILE) * (int64_t) sizeof(T));
         }
-    };
+        // LDS-DMA through a buffer descriptor: the chunk base is a scalar pointer (SALU), the per-lane part
+        // is the constant doff and the panel offset goes in soffset — no VALU address math per chunk
+        const uint32_t offI = __builtin_amdgcn_readfirstlane((uint32_t) (I0 * (int64_t) sizeof(T)));
+        const uint32_t offJ = __builtin_amdgcn_readfirstlane((uint32_t) (J0 * (int64_t) sizeof(T)));
+        auto issue = [&](int64_t kc, int buf) {
+            const T *cb = XT + kc * BK * n_pad;
+            T *pa = smem + OFF_PAN + (2 * buf) * PANEL;
+            T *pb = pa + PANEL;
+#pragma unroll
+            for (int j = 0; j < PIECES; ++j) {
+                const int u = w * PIECES + j;
+                glds16_buf(cb, pa + u * EPP, doff[j], offI);
+                glds16_buf(cb, pb + u * EPP, doff[j], offJ);
+            }
+        };
 
-    acc_t acc[4][4];
 #pragma unroll
-    for (int a = 0; a < 4; ++a)
+        for (int a = 0; a < 4; ++a)
 #pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = acc_t{ acc0[b], acc0[b], acc0[b], acc0[b] };
+            for (int b = 0; b < 4; ++b) acc[a][b] = acc_t{ acc0[b], acc0[b], acc0[b], acc0[b] };
 
-    issue(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    smem[tid] = pin;
-    smem[2 * KP_TILE + tid] = nin;
-    if constexpr (FAST_EXP) {
-        if (tid < EXP_TAB) exp_tab[tid] = c_exp2_256[tid];  // visible after the first K-loop barrier
-    }
-
-    const int64_t nk = d_pad / BK;
-    for (int64_t kc = 0; kc < nk; ++kc) {
-        if (kc > 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();  // chunk kc visible to all waves; every wave is done reading chunk kc-1
-        if (!kp_dma_after_reads<T, KERNEL>() && kc + 1 < nk) issue(kc + 1, (int) ((kc + 1) & 1));
-        const T *A = smem + OFF_PAN + (2 * (kc & 1)) * PANEL;
-        const T *B = A + PANEL;
-        // fp64 RBF: the whole chunk's operands come out of LDS before chunk kc+1's DMA is issued — the compiler cannot
-        // tell the DMA's LDS target from the buffer being read, so an LDS read issued after the DMA waits for it
-        // (vmcnt(0)) and the prefetch sits on each wave's critical path instead of under its MFMAs (the other instances
-        // measured faster with the DMA first, see kp_dma_after_reads)
-        T a[BK / 4][4], b[BK / 4][4];
-#pragma unroll
-        for (int ks = 0; ks < BK / 4; ++ks) {
-            const int kr = ks * 4 + (lane >> 4);
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) a[ks][mt] = A[kr * KP_TILE + wr * 64 + mt * 16 + (lane & 15)];
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) b[ks][nt] = B[kr * KP_TILE + wc * 64 + nt * 16 + (lane & 15)];
+        issue(0, 0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        smem[tid] = pin;
+        smem[2 * KP_TILE + tid] = nin;
+        if constexpr (FAST_EXP) {
+            if (tid < EXP_TAB) exp_tab[tid] = c_exp2_256[tid];  // visible after the first K-loop barrier
         }
-        if (kp_dma_after_reads<T, KERNEL>() && kc + 1 < nk) issue(kc + 1, (int) ((kc + 1) & 1));
+
+        const int64_t nk = d_pad / BK;
+        for (int64_t kc = 0; kc < nk; ++kc) {
+            if (kc > 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();  // chunk kc visible to all waves; every wave is done reading chunk kc-1
+            if (!kp_dma_after_reads<T, KERNEL>() && kc + 1 < nk) issue(kc + 1, (int) ((kc + 1) & 1));
+            const T *A = smem + OFF_PAN + (2 * (kc & 1)) * PANEL;
+            const T *B = A + PANEL;
+            // fp64 RBF: the whole chunk's operands come out of LDS before chunk kc+1's DMA is issued — the compiler cannot
+            // tell the DMA's LDS target from the buffer being read, so an LDS read issued after the DMA waits for it
+            // (vmcnt(0)) and the prefetch sits on each wave's critical path instead of under its MFMAs (the other instances
+            // measured faster with the DMA first, see kp_dma_after_reads)
+            T a[BK / 4][4], b[BK / 4][4];
 #pragma unroll
-        for (int ks = 0; ks < BK / 4; ++ks)
+            for (int ks = 0; ks < BK / 4; ++ks) {
+                const int kr = ks * 4 + (lane >> 4);
 #pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
+                for (int mt = 0; mt < 4; ++mt) a[ks][mt] = A[kr * KP_TILE + wr * 64 + mt * 16 + (lane & 15)];
 #pragma unroll
-                for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = M::op(a[ks][mt], b[ks][nt], acc[mt][nt]);
+                for (int nt = 0; nt < 4; ++nt) b[ks][nt] = B[kr * KP_TILE + wc * 64 + nt * 16 + (lane & 15)];
+            }
+            if (kp_dma_after_reads<T, KERNEL>() && kc + 1 < nk) issue(kc + 1, (int) ((kc + 1) & 1));
+#pragma unroll
+            for (int ks = 0; ks < BK / 4; ++ks)
+#pragma unroll
+                for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                    for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = M::op(a[ks][mt], b[ks][nt], acc[mt][nt]);
+        }
     }
 
     // ---- epilogue: kernel function, times p, row and column partial sums ----
@@ -317,20 +359,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_waves_pe
         for (int r = 0; r < 4; ++r) {
             const int il = wr * 64 + mt * 16 + M::row(lane, r);
             const T pi = pI[il];
-            const T ni = nI[il];
+            const T ni = MODE == KP_LOAD ? T(0) : nI[il];
             const T ai = FAST_EXP ? -kf.gamma * T(KEXP) * ni : T(0);
             T s = 0;
+            T kvs[4];
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) {
                 T kv;
-                if constexpr (FAST_EXP)
+                if constexpr (MODE == KP_LOAD)
+                    kv = kld[((mt * 4 + r) * 4 + nt) / VEC][nt % VEC];
+                else if constexpr (FAST_EXP)
                     kv = (T) exp_scaled_f64(fma(c2, acc[mt][nt][r], ai), exp_tab);
                 else
                     kv = kernel_apply<T>(KERNEL, kf.degree, kf.gamma, kf.coef0, acc[mt][nt][r], ni, nj[nt]);
+                kvs[nt] = kv;
                 s = fma(kv, pj[nt], s);
                 cs[nt] = fma(kv, pi, cs[nt]);
             }
             rowp[il * RSTR + (lane & 15)] = s;
+            if constexpr (MODE == KP_COMPUTE_STORE) {
+                vec_t *rec = reinterpret_cast<vec_t *>(kcache + wg * KP_CACHE_REC) + tid;
+#pragma unroll
+                for (int h = 0; h < 4 / VEC; ++h) {
+                    vec_t v;
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e) v[e] = kvs[h * VEC + e];
+                    rec[((mt * 4 + r) * (4 / VEC) + h) * 256] = v;
+                }
+            }
         }
     }
     if (!diag) {
@@ -423,30 +479,54 @@ __global__ __launch_bounds__(64 * KP_RED_G) void kp_reduce_share_kernel(const T 
 
 }  // namespace
 
+namespace {
+
+// one launch of `count` workgroups (tiles [base, base + count) of the rank's table) in one mode
+template <typename T, int MODE>
+void launch_kp_mode(kfun<T> kf, const T *XT, const T *norms, const T *p, T *partial, int64_t n_pad, int64_t d_pad,
+                    int64_t nb, int64_t s0, int64_t nsuper, const int32_t *wg_off, int64_t base, int64_t count,
+                    const cg_scalars<T> *status, T *kcache, hipStream_t s) {
+    if (count <= 0) return;
+    const dim3 grid((unsigned) count), block(256);
+#define KP_LAUNCH(KERNEL)                                                                                         \
+    hipLaunchKernelGGL((kp_tile_kernel<T, KERNEL, MODE>), grid, block, 0, s, kf, XT, norms, p, partial, n_pad, d_pad, \
+                       nb, s0, nsuper, wg_off, status, base, kcache)
+    if constexpr (MODE == KP_LOAD) {
+        KP_LAUNCH(0);  // one instance per real type: the stored values are past the kernel function
+    } else {
+        switch (kf.kernel) {
+            case 0: KP_LAUNCH(0); break;
+            case 1: KP_LAUNCH(1); break;
+            default: KP_LAUNCH(2); break;
+        }
+    }
+#undef KP_LAUNCH
+    MI_LAUNCH_CHECK();
+}
+
+}  // namespace
+
+// Tiles [0, cached) of the rank's table have a record in kcache: they are streamed from it (KP_LOAD), or, with
+// `fill`, computed and stored (KP_COMPUTE_STORE); tiles [cached, wgs) are computed. cached = 0: one KP_COMPUTE
+// launch over all tiles. Every mode writes the same slab records, so the split never shows in K·p.
 template <typename T>
 void launch_kp_tiles(kfun<T> kf, const T *XT, const T *norms, const T *p, T *partial, int64_t n_pad, int64_t d_pad,
                      int64_t nb, int64_t s0, int64_t nsuper, const int32_t *wg_off, int64_t wgs,
-                     const cg_scalars<T> *status, hipStream_t s) {
+                     const cg_scalars<T> *status, hipStream_t s, T *kcache, int64_t cached, bool fill) {
     if (nsuper <= 0 || nb <= 0 || wgs <= 0) return;
     // 32-bit DMA offsets inside a chunk (kp_tile_kernel): (BK - 1) rows of n_pad plus a tile row
     if ((int64_t) kp_dpad<T>() * n_pad * (int64_t) sizeof(T) >= ((int64_t) 1 << 31))
         throw mi_error(-5, "too many points for the pairwise tile kernel's 32-bit chunk offsets");
-    const dim3 grid((unsigned) wgs), block(256);
-    switch (kf.kernel) {
-        case 0:
-            hipLaunchKernelGGL((kp_tile_kernel<T, 0>), grid, block, 0, s, kf, XT, norms, p, partial, n_pad, d_pad, nb,
-                               s0, nsuper, wg_off, status);
-            break;
-        case 1:
-            hipLaunchKernelGGL((kp_tile_kernel<T, 1>), grid, block, 0, s, kf, XT, norms, p, partial, n_pad, d_pad, nb,
-                               s0, nsuper, wg_off, status);
-            break;
-        default:
-            hipLaunchKernelGGL((kp_tile_kernel<T, 2>), grid, block, 0, s, kf, XT, norms, p, partial, n_pad, d_pad, nb,
-                               s0, nsuper, wg_off, status);
-            break;
-    }
-    MI_LAUNCH_CHECK();
+    if (kcache == nullptr || cached < 0) cached = 0;
+    if (cached > wgs) cached = wgs;
+    if (fill)
+        launch_kp_mode<T, KP_COMPUTE_STORE>(kf, XT, norms, p, partial, n_pad, d_pad, nb, s0, nsuper, wg_off, 0, cached,
+                                            status, kcache, s);
+    else
+        launch_kp_mode<T, KP_LOAD>(kf, XT, norms, p, partial, n_pad, d_pad, nb, s0, nsuper, wg_off, 0, cached, status,
+                                   kcache, s);
+    launch_kp_mode<T, KP_COMPUTE>(kf, XT, norms, p, partial, n_pad, d_pad, nb, s0, nsuper, wg_off, cached, wgs - cached,
+                                  status, nullptr, s);
 }
 
 // Both the whole triangle and a rank's share use the wave-split reduction (16 waves per 64 rows, each a
@@ -464,7 +544,7 @@ void launch_kp_reduce(const T *partial, int64_t nb, int64_t m, int64_t s0, int64
 #define INST(T)                                                                                                  \
     template void launch_kp_tiles<T>(kfun<T>, const T *, const T *, const T *, T *, int64_t, int64_t, int64_t, \
                                      int64_t, int64_t, const int32_t *, int64_t, const cg_scalars<T> *,        \
-                                     hipStream_t);                                                              \
+                                     hipStream_t, T *, int64_t, bool);                                          \
     template void launch_kp_reduce<T>(const T *, int64_t, int64_t, int64_t, int64_t, const int32_t *, T *,     \
                                       const cg_scalars<T> *, hipStream_t);
 INST(float)

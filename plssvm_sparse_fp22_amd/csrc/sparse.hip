@@ -1043,7 +1043,7 @@ void engine<T>::setup_csr(const int64_t *rowptr, const int32_t *col, const void 
         if (sparse_algo == 2 && !elig)
             throw mi_error(-5, "the kernel expansion cannot represent this kernel on this data (Taylor degree > 16 or "
                                "the factored rbf form out of range): use the Gram pattern");
-        int64_t budget = sparse_mem_budget();
+        int64_t budget = mem_budget();
         const bool use_exp = elig && sparse_algo != 1;
         const bool unstored = sparse_algo == 3 || sparse_algo == 4;  // forced densified / on the fly
         if (!unstored) {
@@ -1232,10 +1232,11 @@ void engine<T>::setup_csr(const int64_t *rowptr, const int32_t *col, const void 
     }
 }
 
-// device bytes the stored sparse structures may use: 85 % of the free memory (PLSSVM_MI_MEM_BUDGET =
-// bytes overrides it, tests force the densified path with it)
+// device bytes the stored per-pair structures (sparse Gram pattern, expansion remainder, dense tile cache) may use:
+// 85 % of the memory free at the time of the call (PLSSVM_MI_MEM_BUDGET = bytes overrides it, tests force the
+// densified path and partial tile caches with it)
 template <typename T>
-int64_t engine<T>::sparse_mem_budget() const {
+int64_t engine<T>::mem_budget() const {
     if (const char *e = std::getenv("PLSSVM_MI_MEM_BUDGET")) {
         const long long v = std::atoll(e);
         if (v > 0) return (int64_t) v;
@@ -1330,6 +1331,7 @@ void engine<T>::setup_sparse_dense() {
     MI_LAUNCH_CHECK();
     MI_HIP_CHECK(hipStreamSynchronize(stream));
     csr.dense_on = true;
+    kcache_setup();
 }
 
 template <typename T>
