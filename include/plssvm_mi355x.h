@@ -113,6 +113,12 @@ extern "C" {
  *   0 = auto (on where it fits), 1 = off. Environment PLSSVM_MI_KP_CACHE=0, read at setup, also turns it off. */
 #define PLSSVM_MI_OPT_KP_CACHE 6
 
+/* Width of the multi-right-hand-side calls (plssvm_mi_kp_multi, _solve_cg_multi, _learn_multi): how many vectors one
+ * pass over the kernel-matrix tiles serves. 0 = auto (up to 8, halved until the lanes' device memory fits beside the
+ * tile cache), 1 = always one vector at a time through the single-vector code, n >= 2 = at most n (capped at 8). More
+ * right-hand sides than the width run in groups, in order. plssvm_mi_info.multi_width reports the width in use. */
+#define PLSSVM_MI_OPT_MULTI_WIDTH 7
+
 typedef struct plssvm_mi_ctx plssvm_mi_ctx;
 
 /* Number of visible HIP devices (>= 0), or a negative error code. */
@@ -251,6 +257,38 @@ PLSSVM_MI_API int plssvm_mi_cg_result(plssvm_mi_ctx *ctx, void *x_out, double *d
 PLSSVM_MI_API int plssvm_mi_learn(plssvm_mi_ctx *ctx, const void *y, int64_t imax, double eps, void *alpha_out, double *bias_out,
                     double *delta_trace, int64_t *iters);
 
+/* Several right-hand sides at once (build-defined; the reference trains one binary problem per solve): the K
+ * one-vs-all systems of a K-class problem share Q~ and differ only in b, so on the pairwise tile path of a single
+ * GPU every CG iteration visits each kernel-matrix tile once for all of them (plssvm_mi_info.multi_width >= 2).
+ * Everywhere else (stored sparse paths, the factored linear path, groups, simulated ranks, the one-reduction CG, or
+ * too little free device memory for two lanes) the same calls run the vectors one after another. Either way every
+ * column is BITWISE what the single-vector call returns for it, whatever the width, grouping or tile-cache state.
+ * All matrices are row-major with one vector per row and leading dimension ld: vector c starts at base + c * ld
+ * reals; ld >= m (>= n for the label and alpha matrices); elements past m (n) of a row are never read or written.
+ * nrhs / nclass < 1, a NULL buffer or a too small ld: PLSSVM_MI_ERR_ARG. nrhs == 1 equals the single call. The
+ * progress callback is not called by these entry points.
+ *
+ * plssvm_mi_kp_multi: RET_c += add * Q~ P_c for c < nrhs; each row as plssvm_mi_kp (q NULL = the context's q). */
+PLSSVM_MI_API int plssvm_mi_kp_multi(plssvm_mi_ctx *ctx, const void *q, const void *P, void *RET, int64_t nrhs, int64_t ld,
+                                     double add);
+/* plssvm_mi_solve_cg_multi: plssvm_mi_solve_cg for the right-hand sides B[nrhs][ld] (q NULL = the context's q):
+ * X_out[nrhs][ld]; delta_trace nullable, [nrhs][imax + 1], row c filled up to iters[c]; iters[nrhs] (nullable). Every
+ * right-hand side keeps its own alpha, beta, delta, stop test and iteration count; one that has converged is frozen
+ * while the others go on, and the call returns when all have converged or imax is reached. */
+PLSSVM_MI_API int plssvm_mi_solve_cg_multi(plssvm_mi_ctx *ctx, const void *B, int64_t nrhs, int64_t ld, const void *q,
+                                           int64_t imax, double eps, void *X_out, double *delta_trace, int64_t *iters);
+/* plssvm_mi_learn_multi: plssvm_mi_learn per class of a one-vs-all label matrix Y[nclass][ldy], ldy >= n, row c
+ * holding +1 for the points of class c and -1 for all others. Per class exactly plssvm_mi_learn's arithmetic
+ * (b = y - y_m, the bias, alpha[m] = -sum): alpha_out[nclass][ldy], bias_out[nclass] (nullable), delta_trace
+ * (nullable, [nclass][imax + 1]; with imax < 0: [nclass][num_features + 1]), iters[nclass] (nullable). The class with
+ * the largest decision value bias_c + sum_i alpha_ci k(x_i, z) is the prediction (plssvm_mi_predict_* per class). */
+PLSSVM_MI_API int plssvm_mi_learn_multi(plssvm_mi_ctx *ctx, const void *Y, int64_t nclass, int64_t ldy, int64_t imax,
+                                        double eps, void *alpha_out, double *bias_out, double *delta_trace,
+                                        int64_t *iters);
+/* Timing hook: plssvm_mi_time_kp's K·p time for the product with nrhs resident vectors (in groups of the width; one at
+ * a time where nothing is batched), averaged over `reps` products, measured with hipEvents on the context's stream. */
+PLSSVM_MI_API int plssvm_mi_time_kp_multi(plssvm_mi_ctx *ctx, int64_t nrhs, int reps, double *ms_per_kp);
+
 /* gpu_csvm::update_w (src/plssvm/backends/gpu_csvm.cpp:327-350; OpenMP csvm.cpp:174-190):
  * w_out[d] = sum_i alpha_i x_i over all n points of the context's data (alpha[n], e.g. from
  * plssvm_mi_learn, alpha[m] included). Linear kernel model vector. */
@@ -304,6 +342,8 @@ typedef struct {
     int64_t kp_cache_tiles; /* pairwise tile path: tiles of this rank whose kernel values are kept in HBM
                                (PLSSVM_MI_OPT_KP_CACHE); tiles_local when all fit, 0 = none */
     int64_t kp_cache_bytes; /* device bytes of those records (tile_rows x tile_cols reals each) */
+    int multi_width;        /* vectors the next multi-right-hand-side call serves per pass over the tiles
+                               (PLSSVM_MI_OPT_MULTI_WIDTH); 1 = not batched: one vector at a time */
 } plssvm_mi_info;
 PLSSVM_MI_API int plssvm_mi_get_info(const plssvm_mi_ctx *ctx, plssvm_mi_info *info);
 

@@ -25,7 +25,7 @@ from . import io as _io
 from .io import parse_libsvm, parse_model, read_binary, write_binary
 
 __all__ = ["Parameter", "CSVM", "BackendError", "parse_libsvm", "parse_model", "read_binary", "write_binary",
-           "device_count", "unique_id", "partition", "torch_exchange"]
+           "device_count", "unique_id", "partition", "torch_exchange", "one_vs_all"]
 
 
 def device_count() -> int:
@@ -89,6 +89,32 @@ def torch_exchange(dist, group=None):
             buf[:] = acc
 
     return fn
+
+
+def one_vs_all(labels, dtype=np.float64):
+    """One-vs-all coding of integer or float class labels: (classes, Y) with the sorted unique labels and the
+    [K][n] matrix of +1 (the point is of class k) / -1 in the real type ``dtype`` — plssvm_mi_learn_multi's Y."""
+    labels = np.asarray(labels)
+    if labels.ndim != 1 or labels.size == 0:
+        raise ValueError("labels must be a non-empty 1-D array")
+    if not (np.issubdtype(labels.dtype, np.integer) or np.issubdtype(labels.dtype, np.floating)):
+        raise ValueError("class labels must be integers or floats")
+    if np.issubdtype(labels.dtype, np.floating) and not np.isfinite(labels).all():
+        raise ValueError("class labels must be finite")
+    classes = np.unique(labels)
+    one = np.dtype(dtype).type(1)
+    Y = np.where(labels[None, :] == classes[:, None], one, -one).astype(dtype)
+    return classes, np.ascontiguousarray(Y)
+
+
+def _rows(a, dtype, m, what):
+    """[R][ld] row-major matrix of the real type with ld >= m (a 1-D vector counts as one row)."""
+    a = np.ascontiguousarray(np.atleast_2d(a), dtype=dtype)
+    if a.ndim != 2 or a.shape[0] < 1:
+        raise ValueError(f"{what} must be a [vectors][length] matrix with at least one vector")
+    if a.shape[1] < m:
+        raise ValueError(f"{what} rows must have at least {m} entries")
+    return a
 
 
 def _ptr(a):
@@ -158,7 +184,8 @@ class CSVM:
     """One MI355X context (one GPU, one HIP stream). ``world_size > 1`` joins a row-block group."""
 
     def __init__(self, params: Parameter, device=0, rank=0, world_size=1, uid=None, kp_mode="auto",
-                 sim_rank=None, rbf_form=0, exchange=None, sparse_algo="auto", cg_variant=None, kp_cache=None):
+                 sim_rank=None, rbf_form=0, exchange=None, sparse_algo="auto", cg_variant=None, kp_cache=None,
+                 multi_width=None):
         if params.data is None and params.csr is None and params.coo is None:
             raise ValueError("No data points provided!")
         if params.data is not None:
@@ -189,6 +216,8 @@ class CSVM:
             self._check(L.plssvm_mi_set_option(self._ctx, _abi.OPT_CG_VARIANT, v))
         if kp_cache is not None:  # False: never store kernel-matrix tiles, see PLSSVM_MI_OPT_KP_CACHE
             self._check(L.plssvm_mi_set_option(self._ctx, _abi.OPT_KP_CACHE, 0 if kp_cache else 1))
+        if multi_width is not None:  # 0 auto, 1 one vector at a time, n: at most n lanes, see PLSSVM_MI_OPT_MULTI_WIDTH
+            self._check(L.plssvm_mi_set_option(self._ctx, _abi.OPT_MULTI_WIDTH, int(multi_width)))
         if sim_rank is not None:  # (rank, world): single-GPU test hook, see PLSSVM_MI_OPT_SIM_RANK
             self._check(L.plssvm_mi_set_option(self._ctx, _abi.OPT_SIM_RANK, sim_rank[0] | (sim_rank[1] << 16)))
         if exchange is not None:  # host-staged group: fn(numpy buffer, op) combines in place (torch_exchange)
@@ -207,6 +236,11 @@ class CSVM:
         self.bias = None
         self.trace = None
         self.iters = None
+        self.classes = None  # learn_multi: sorted class labels, alphas [K][n], biases [K]
+        self.alphas = None
+        self.biases = None
+        self.iters_multi = None
+        self.traces = None
         self._on_device = False
 
     @staticmethod
@@ -339,6 +373,78 @@ class CSVM:
         self.iters = it.value
         self.trace = trace[: it.value + 1]
         return self
+
+    # ---- several right-hand sides / classes at once (plssvm_mi_*_multi) ----
+    def run_device_kernel_multi(self, q, RET, P, add):
+        """RET[c] += add * Q~ P[c] for every row c; rows may be longer than m (the tail is never touched). Each row is
+        bitwise run_device_kernel of that row."""
+        assert RET.dtype == self.dtype and RET.flags.c_contiguous and RET.ndim == 2
+        qq = None if q is None else np.ascontiguousarray(q, dtype=self.dtype)
+        PP = _rows(P, self.dtype, self.m, "P")
+        if PP.shape != RET.shape:
+            raise ValueError("P and RET must have the same shape")
+        self._check(_abi.lib().plssvm_mi_kp_multi(self._ctx, _ptr(qq), _ptr(PP), _ptr(RET), PP.shape[0], PP.shape[1],
+                                                  float(add)))
+        return RET
+
+    def solver_CG_multi(self, B, imax, eps, q=None):
+        """solver_CG for every row of B[R][>= m]; returns X[R][m] and sets iters_multi [R] and traces (R arrays)."""
+        BB = _rows(B, self.dtype, self.m, "B")
+        R, ld = BB.shape
+        qq = None if q is None else np.ascontiguousarray(q, dtype=self.dtype)
+        X = np.zeros((R, ld), dtype=self.dtype)
+        trace = np.full((R, imax + 1), np.nan)
+        it = np.zeros(R, dtype=np.int64)
+        self._check(_abi.lib().plssvm_mi_solve_cg_multi(self._ctx, _ptr(BB), R, ld, _ptr(qq), imax, float(eps), _ptr(X),
+                                                        _ptr(trace), _ptr(it)))
+        self.iters_multi = it
+        self.traces = [trace[c, : it[c] + 1].copy() for c in range(R)]
+        return X[:, : self.m]
+
+    def learn_multi(self, labels=None, imax=-1):
+        """One-vs-all training on K >= 2 classes (any integer or float labels; default: the parameter's labels): per
+        class exactly learn() on the +-1 labels of that class against the rest, the K solves sharing each pass over
+        the kernel matrix. Sets classes [K], alphas [K][n], biases [K], iters_multi [K], traces."""
+        labels = self.params.labels if labels is None else labels
+        if labels is None:
+            raise ValueError("No labels given for training! Maybe the data is only usable for prediction?")
+        classes, Y = one_vs_all(labels, self.dtype)
+        if Y.shape[1] != self.num_data_points:
+            raise ValueError(f"labels must have {self.num_data_points} entries")
+        if classes.size < 2:
+            raise ValueError("learn_multi needs at least 2 classes")
+        if not self._on_device:
+            self.setup_data_on_device()
+        K, n = Y.shape
+        im = self.num_features if imax < 0 else imax
+        alphas = np.zeros((K, n), dtype=self.dtype)
+        biases = np.zeros(K, dtype=np.float64)
+        trace = np.full((K, im + 1), np.nan)
+        it = np.zeros(K, dtype=np.int64)
+        self._check(_abi.lib().plssvm_mi_learn_multi(self._ctx, _ptr(Y), K, n, im, float(self.params.epsilon),
+                                                     _ptr(alphas), _ptr(biases), _ptr(trace), _ptr(it)))
+        self.classes = classes
+        self.alphas = alphas
+        self.biases = biases.astype(self.dtype)
+        self.iters_multi = it
+        self.traces = [trace[c, : it[c] + 1].copy() for c in range(K)]
+        return self
+
+    def predict_values_multi(self, points, val_fmt=None):
+        """Decision values [np][K] of the learn_multi model: column k is predict_values with class k's alpha, bias."""
+        if self.alphas is None:
+            raise ValueError("No alphas provided for prediction!")
+        return np.stack([self.predict_values(points, self.alphas[k], self.biases[k], val_fmt)
+                         for k in range(len(self.classes))], axis=1)
+
+    def predict_multi(self, points, val_fmt=None):
+        """The class with the largest decision value (the lowest class index on a tie)."""
+        return self.classes[np.argmax(self.predict_values_multi(points, val_fmt), axis=1)]
+
+    def time_kp_multi(self, nrhs, reps=5):
+        a = ctypes.c_double()
+        self._check(_abi.lib().plssvm_mi_time_kp_multi(self._ctx, int(nrhs), reps, ctypes.byref(a)))
+        return a.value
 
     # ---- model use: update_w / predict / accuracy (csvm.hpp:123-178, gpu_csvm.cpp:52-127,327-350) ----
     def _model(self, alpha, bias):

@@ -32,12 +32,14 @@ EXPORTS = (
     "plssvm_mi_time_kp", "plssvm_mi_get_info", "plssvm_mi_partition",
     "plssvm_mi_update_w", "plssvm_mi_predict_dense", "plssvm_mi_predict_csr", "plssvm_mi_setup_coo",
     "plssvm_mi_comm_init_host", "plssvm_mi_kp_part", "plssvm_mi_set_progress", "plssvm_mi_comm_abort",
+    "plssvm_mi_kp_multi", "plssvm_mi_solve_cg_multi", "plssvm_mi_learn_multi", "plssvm_mi_time_kp_multi",
 )
 OPT_SIM_RANK = 2
 OPT_RBF_FORM = 3
 OPT_SPARSE_ALGO = 4
 OPT_CG_VARIANT = 5
 OPT_KP_CACHE = 6
+OPT_MULTI_WIDTH = 7
 SPARSE_AUTO, SPARSE_PATTERN, SPARSE_EXPANSION, SPARSE_DENSE, SPARSE_ONTHEFLY = 0, 1, 2, 3, 4
 PART_KERNEL, PART_OVERLAP, PART_REMAINDER = 0, 1, 2
 XCHG_ALLREDUCE, XCHG_ALLGATHER = 0, 1
@@ -57,7 +59,8 @@ class Info(ctypes.Structure):
                [("rbf_small_args", ctypes.c_int), ("sparse_algo", ctypes.c_int), ("exp_terms", ctypes.c_int),
                 ("exp_waves", ctypes.c_int), ("exp_chunks", ctypes.c_int64), ("exp_hbytes", ctypes.c_int),
                 ("exp_layout", ctypes.c_int), ("exp_dot2", ctypes.c_int), ("centered", ctypes.c_int),
-                ("exp_lt", ctypes.c_int), ("kp_cache_tiles", ctypes.c_int64), ("kp_cache_bytes", ctypes.c_int64)]
+                ("exp_lt", ctypes.c_int), ("kp_cache_tiles", ctypes.c_int64), ("kp_cache_bytes", ctypes.c_int64),
+                ("multi_width", ctypes.c_int)]
 
 
 class BackendError(RuntimeError):
@@ -117,6 +120,10 @@ def _declare(L):
         "plssvm_mi_kp_part": ([P, P, P, I], I),
         "plssvm_mi_comm_abort": ([P], I),
         "plssvm_mi_set_progress": ([P, PROGRESS_FN, P], I),
+        "plssvm_mi_kp_multi": ([P, P, P, P, I64, I64, D], I),
+        "plssvm_mi_solve_cg_multi": ([P, P, I64, I64, P, I64, D, P, P, P], I),
+        "plssvm_mi_learn_multi": ([P, P, I64, I64, I64, D, P, P, P, P], I),
+        "plssvm_mi_time_kp_multi": ([P, I64, I, PD], I),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

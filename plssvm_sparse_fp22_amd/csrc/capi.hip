@@ -115,6 +115,8 @@ int plssvm_mi_set_option(plssvm_mi_ctx *ctx, int key, int64_t value) {
             e.cg_variant = (int) value;
         } else if (key == PLSSVM_MI_OPT_KP_CACHE && value >= 0 && value <= 1) {
             e.kp_cache_opt = (int) value;
+        } else if (key == PLSSVM_MI_OPT_MULTI_WIDTH && value >= 0 && value <= 1024) {
+            e.multi_opt = (int) value;
         } else {
             throw mi_error(PLSSVM_MI_ERR_ARG, "bad option");
         }
@@ -337,6 +339,39 @@ int plssvm_mi_time_kp(plssvm_mi_ctx *ctx, int reps, double *ms_per_kp, double *m
     return ctx->call([&](auto &e) { e.time_kp(reps, ms_per_kp, ms_dominant_kernel); });
 }
 
+int plssvm_mi_kp_multi(plssvm_mi_ctx *ctx, const void *q, const void *P, void *RET, int64_t nrhs, int64_t ld, double add) {
+    if (!ctx || !P || !RET || nrhs < 1) return PLSSVM_MI_ERR_ARG;
+    return ctx->call([&](auto &e) {
+        using T = std::remove_reference_t<decltype(e.gamma)>;
+        e.kp_multi(static_cast<const T *>(q), static_cast<const T *>(P), static_cast<T *>(RET), nrhs, ld, (T) add);
+    });
+}
+
+int plssvm_mi_solve_cg_multi(plssvm_mi_ctx *ctx, const void *B, int64_t nrhs, int64_t ld, const void *q, int64_t imax,
+                             double eps, void *X_out, double *delta_trace, int64_t *iters) {
+    if (!ctx || !B || !X_out || nrhs < 1) return PLSSVM_MI_ERR_ARG;
+    return ctx->call([&](auto &e) {
+        using T = std::remove_reference_t<decltype(e.gamma)>;
+        e.solve_cg_multi(static_cast<const T *>(B), nrhs, ld, static_cast<const T *>(q), imax, (T) eps,
+                         static_cast<T *>(X_out), delta_trace, iters);
+    });
+}
+
+int plssvm_mi_learn_multi(plssvm_mi_ctx *ctx, const void *Y, int64_t nclass, int64_t ldy, int64_t imax, double eps,
+                          void *alpha_out, double *bias_out, double *delta_trace, int64_t *iters) {
+    if (!ctx || !Y || !alpha_out || nclass < 1) return PLSSVM_MI_ERR_ARG;
+    return ctx->call([&](auto &e) {
+        using T = std::remove_reference_t<decltype(e.gamma)>;
+        e.learn_multi(static_cast<const T *>(Y), nclass, ldy, imax, (T) eps, static_cast<T *>(alpha_out), bias_out,
+                      delta_trace, iters);
+    });
+}
+
+int plssvm_mi_time_kp_multi(plssvm_mi_ctx *ctx, int64_t nrhs, int reps, double *ms_per_kp) {
+    if (!ctx || nrhs < 1) return PLSSVM_MI_ERR_ARG;
+    return ctx->call([&](auto &e) { e.time_kp_multi(nrhs, reps, ms_per_kp); });
+}
+
 int plssvm_mi_update_w(plssvm_mi_ctx *ctx, const void *alpha, void *w_out) {
     if (!ctx) return PLSSVM_MI_ERR_ARG;
     return ctx->call([&](auto &e) {
@@ -410,6 +445,7 @@ int plssvm_mi_get_info(const plssvm_mi_ctx *cctx, plssvm_mi_info *info) {
         info->exp_lt = e.csr.ex.on && e.csr.ex.lt ? 1 : 0;
         info->kp_cache_tiles = e.kcache_tiles;
         info->kp_cache_bytes = e.kcache.bytes();
+        info->multi_width = e.multi_width_next();
     });
 }
 

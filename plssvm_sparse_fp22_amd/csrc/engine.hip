@@ -364,6 +364,7 @@ void engine<T>::setup_dense(const T *X, int64_t n_, int64_t d_) {
 
 template <typename T>
 void engine<T>::finish_setup() {
+    lanes = lane_pool{};  // an earlier setup's lanes go before the tile cache is sized; the first multi call allocates anew
     // work split of the implicit matrix over the group (replaces feature_ranges_, gpu_csvm.cpp:136-139)
     partition_superblocks(nb, sim_world > 0 ? sim_rank : rank, sim_world > 0 ? sim_world : world, t0, t1, t_total,
                           tiles_total, tiles_local);
@@ -994,10 +995,332 @@ void engine<T>::time_kp(int reps, double *ms_kp, double *ms_dom) {
     if (ms_dom) *ms_dom = dom / reps;
 }
 
+// ---- several right-hand sides over one pass of the tiles (engine.hpp "lanes") -------------------
+
+// The batched path: the pairwise tile path on one rank with the reference recurrence. There G = 1, v0 = 0, vn = m,
+// no collective, no centered finalize and no w pass riding with the direction update, which is what the lane code
+// below relies on. Everything else runs the right-hand sides one after another through the single-vector code.
+template <typename T>
+bool engine<T>::multi_batched() const {
+    const bool tiles_path = !factored() && (!sparse || csr.dense_on);
+    return have_data && tiles_path && m > 0 && kp_wgs > 0 && world == 1 && comm == nullptr && xchg == nullptr &&
+           sim_world == 0 && !shard && !cg1_wanted() && multi_opt != 1;
+}
+
+template <typename T>
+int64_t engine<T>::lane_bytes() const {
+    return ((int64_t) LV_COUNT * q.size() + kp_wgs * KP_REC + 8 * RED_BLOCKS) * (int64_t) sizeof(T) +
+           (int64_t) sizeof(cg_scalars<T>);
+}
+
+// Lanes are taken from what the setup (tile cache included) left free, keeping 256 MiB for the single path's own
+// later needs (traces, a captured block): the widest of W, W / 2, ... that fits; 1 = not even two lanes fit.
+template <typename T>
+int engine<T>::multi_width_next() const {
+    if (!multi_batched()) return 1;
+    if (lanes.width > 0) return lanes.width;
+    size_t free_b = 0, total_b = 0;
+    MI_HIP_CHECK(hipSetDevice(device));
+    MI_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    const int64_t room = (int64_t) free_b - ((int64_t) 256 << 20);
+    int w = multi_opt >= 2 ? std::min(multi_opt, KP_MULTI_W) : KP_MULTI_W;
+    while (w >= 2 && (int64_t) w * lane_bytes() > room) w /= 2;
+    return std::max(w, 1);
+}
+
+template <typename T>
+int engine<T>::multi_lanes() {
+    if (!multi_batched()) return 1;
+    if (lanes.width > 0) return lanes.width;
+    for (int w = multi_width_next(); w >= 2; w /= 2) {
+        try {
+            lanes.vstride = q.size();
+            lanes.sstride = kp_wgs * KP_REC;
+            lanes.vec.alloc((int64_t) LV_COUNT * w * lanes.vstride, stream);
+            lanes.slab.alloc((int64_t) w * lanes.sstride, stream, false);
+            lanes.part.alloc((int64_t) w * 8 * RED_BLOCKS, stream);
+            lanes.sc.alloc(w, stream);
+            lanes.width = w;
+            return w;
+        } catch (const mi_error &e) {
+            if (e.code != -4) throw;
+            (void) hipGetLastError();
+            lanes = lane_pool{};
+        }
+    }
+    lanes.width = 1;
+    return 1;
+}
+
+// One pass over the tiles for the vectors `kind` of lanes [c0, c0 + nvec); flags: the lanes' stop flags apply.
+// The stored records are streamed once they are filled; filling them is the single-vector path's job.
+template <typename T>
+void engine<T>::tiles_multi(int kind, int c0, int nvec, bool flags) {
+    launch_kp_tiles_multi<T>(kf(), XT.get(), norms.get(), lane_v(kind, c0), lanes.vstride,
+                             lanes.slab.get() + (int64_t) c0 * lanes.sstride, lanes.sstride, nvec, n_pad, d_pad, nb, t0,
+                             t1 - t0, kp_wgoff.get(), kp_wgs, flags ? lanes.sc.get() + c0 : nullptr, stream, kcache.get(),
+                             kcache_valid ? kcache_tiles : 0);
+}
+
+// kp_device's first half for p = lane c's x0 = 1 on the engine's own buffers: sum p, sum q p in sc, the pairwise
+// part in raw. The same for every right-hand side, so one product serves a whole group; with no stop flag it also
+// fills an unfilled tile cache (kp_tiles_now).
+template <typename T>
+void engine<T>::multi_first_product(int c) {
+    const T *x0 = lane_v(LV_X, c);
+    MI_HIP_CHECK(hipMemsetAsync(sc.get(), 0, sizeof(cg_scalars<T>), stream));
+    launch_dot2<T>(x0, nullptr, qf(), x0, m, red.get(), nullptr, stream);
+    launch_dot_final<T>(red.get(), sc.get(), FIN_SP_SQP, 0, nullptr, 0, nullptr, stream, 1);
+    kp_raw(x0, nullptr);
+}
+
+// cg_iter for nvec lanes: one batched tile launch on the direction vectors, then cg_iter's launches per lane
+template <typename T>
+void engine<T>::cg_iter_multi(int nvec, int reset) {
+    tiles_multi(LV_D, 0, nvec, true);
+    for (int c = 0; c < nvec; ++c) {
+        cg_scalars<T> *st = lanes.sc.get() + c;
+        T *psum = lane_cgp(c), *pdad = psum + 2 * RED_BLOCKS, *prr = psum + 4 * RED_BLOCKS;
+        launch_kp_reduce<T>(lanes.slab.get() + (int64_t) c * lanes.sstride, nb, m, t0, t1, kp_wgoff.get(),
+                            lane_v(LV_RAW, c), st, stream);
+        launch_cg_fin_dad<T>(lane_v(LV_RAW, c), nullptr, 0, m, qf(), lane_v(LV_D, c), psum, 1, QAf(), cost_inv(), 0, m,
+                             lane_v(LV_AD, c), pdad, st, stream);
+        launch_cg_upd_rr<T>(lane_v(LV_X, c), lane_v(LV_R, c), lane_v(LV_D, c), lane_v(LV_AD, c), lane_v(LV_B, c), reset,
+                            pdad, 1, m, prr, st, stream);
+    }
+    if (reset) {  // r = b - Q~x: kp_device on the x vectors, one pass over the tiles
+        for (int c = 0; c < nvec; ++c) {
+            cg_scalars<T> *st = lanes.sc.get() + c;
+            launch_dot2<T>(lane_v(LV_X, c), nullptr, qf(), lane_v(LV_X, c), m, lane_red(c), st, stream);
+            launch_dot_final<T>(lane_red(c), st, FIN_SP_SQP, 0, nullptr, 0, nullptr, stream, 1);
+        }
+        tiles_multi(LV_X, 0, nvec, true);
+        for (int c = 0; c < nvec; ++c) {
+            cg_scalars<T> *st = lanes.sc.get() + c;
+            launch_kp_reduce<T>(lanes.slab.get() + (int64_t) c * lanes.sstride, nb, m, t0, t1, kp_wgoff.get(),
+                                lane_v(LV_RAW, c), st, stream);
+            launch_kp_finalize<T>(lane_v(LV_RAW, c), qf(), lane_v(LV_X, c), st, QAf(), cost_inv(), T(-1), 0, m,
+                                  lane_v(LV_R, c), st, stream);
+            launch_dot2<T>(lane_v(LV_R, c), lane_v(LV_R, c), nullptr, nullptr, m, lane_cgp(c) + 4 * RED_BLOCKS, st, stream);
+        }
+    }
+    for (int c = 0; c < nvec; ++c)
+        launch_cg_dir_sums<T>(lane_v(LV_D, c), lane_v(LV_R, c), qf(), lane_cgp(c) + 4 * RED_BLOCKS, 1, 0,
+                              lanes.trace.get() + (int64_t) c * lanes.trace_cap, lanes.trace_cap, m, lane_cgp(c),
+                              lanes.sc.get() + c, stream);
+}
+
+// solve_cg for nvec <= width right-hand sides (B[c * ld + i]) as lanes 0 .. nvec - 1; q is set
+template <typename T>
+void engine<T>::solve_cg_group(const T *B, int nvec, int64_t ld, int64_t imax, T eps, T *X_out, double *trace_out,
+                               int64_t *iters) {
+    // cg_begin per lane
+    cg_scalars<T> init{};
+    init.eps2delta0 = eps * eps;
+    init.g1[0] = init.g1[1] = init.a1[0] = init.a1[1] = std::numeric_limits<T>::infinity();
+    const std::vector<cg_scalars<T>> inits((size_t) nvec, init);
+    MI_HIP_CHECK(hipMemcpyAsync(lanes.sc.get(), inits.data(), sizeof(init) * (size_t) nvec, hipMemcpyHostToDevice, stream));
+    const int64_t cap = imax + 1;
+    if (lanes.trace_cap != cap) {  // a lane's trace has the single solve's length (the kernels' bound)
+        lanes.trace.alloc((int64_t) lanes.width * cap, stream);
+        lanes.trace_cap = cap;
+    } else {
+        MI_HIP_CHECK(hipMemsetAsync(lanes.trace.get(), 0, sizeof(double) * (size_t) lanes.trace.size(), stream));
+    }
+    for (int c = 0; c < nvec; ++c) {
+        MI_HIP_CHECK(hipMemcpyAsync(lane_v(LV_B, c), B + c * ld, sizeof(T) * (size_t) m, hipMemcpyHostToDevice, stream));
+        launch_cg_init<T>(lane_v(LV_B, c), m, lane_v(LV_X, c), lane_v(LV_R, c), stream);  // x = 1; r = b
+    }
+    multi_first_product(0);  // r -= Q~x: x0 is the same for every lane, so is the product
+    for (int c = 0; c < nvec; ++c) {
+        cg_scalars<T> *st = lanes.sc.get() + c;
+        launch_kp_finalize<T>(raw.get(), qf(), lane_v(LV_X, c), sc.get(), QAf(), cost_inv(), T(-1), 0, m, lane_v(LV_R, c),
+                              nullptr, stream);
+        launch_dot2<T>(lane_v(LV_R, c), lane_v(LV_R, c), nullptr, nullptr, m, lane_red(c), nullptr, stream);
+        launch_dot_final<T>(lane_red(c), st, FIN_DELTA0, 0, lanes.trace.get() + (int64_t) c * lanes.trace_cap,
+                            lanes.trace_cap, nullptr, stream, 1);
+        launch_cg_dir_sums<T>(lane_v(LV_D, c), lane_v(LV_R, c), qf(), nullptr, 1, 1, nullptr, 0, m, lane_cgp(c), st, stream);
+    }
+    // solve_cg's polled batches: 4, 8, 16, then up to the first reset, then blocks of CG_RESET; a converged lane's
+    // kernels leave at entry, the group stops when every lane has converged
+    std::vector<cg_scalars<T>> h((size_t) nvec);
+    int64_t done = 0, batch = 4;
+    bool conv = false;
+    while (!conv && done < imax) {
+        const int64_t ns = std::min<int64_t>(done < CG_RESET ? std::min<int64_t>(batch, CG_RESET - done) : CG_RESET,
+                                             imax - done);
+        for (int64_t s = 0; s < ns; ++s, ++done) cg_iter_multi(nvec, done % CG_RESET == CG_RESET - 1 ? 1 : 0);
+        batch *= 2;
+        MI_HIP_CHECK(hipMemcpyAsync(h.data(), lanes.sc.get(), sizeof(init) * (size_t) nvec, hipMemcpyDeviceToHost, stream));
+        MI_HIP_CHECK(hipStreamSynchronize(stream));
+        conv = true;
+        for (int c = 0; c < nvec; ++c) conv = conv && h[(size_t) c].converged != 0;
+    }
+    if (imax == 0 || done == 0) {
+        MI_HIP_CHECK(hipMemcpyAsync(h.data(), lanes.sc.get(), sizeof(init) * (size_t) nvec, hipMemcpyDeviceToHost, stream));
+        MI_HIP_CHECK(hipStreamSynchronize(stream));
+    }
+    for (int c = 0; c < nvec; ++c) {
+        const int64_t it = h[(size_t) c].iters;
+        if (iters) iters[c] = it;
+        MI_HIP_CHECK(hipMemcpyAsync(X_out + c * ld, lane_v(LV_X, c), sizeof(T) * (size_t) m, hipMemcpyDeviceToHost, stream));
+        if (trace_out)
+            MI_HIP_CHECK(hipMemcpyAsync(trace_out + c * cap, lanes.trace.get() + (int64_t) c * lanes.trace_cap,
+                                        sizeof(double) * (size_t) std::min<int64_t>(cap, it + 1), hipMemcpyDeviceToHost, stream));
+    }
+    MI_HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+template <typename T>
+void engine<T>::solve_cg_multi(const T *B, int64_t nrhs, int64_t ld, const T *q_host, int64_t imax, T eps, T *X_out,
+                               double *trace_out, int64_t *iters) {
+    need_data();
+    if (imax < 0) throw mi_error(-1, "imax must be >= 0");
+    if (nrhs < 1) throw mi_error(-1, "at least one right-hand side is needed");
+    if (ld < m) throw mi_error(-1, "the leading dimension is smaller than the number of rows");
+    MI_HIP_CHECK(hipSetDevice(device));
+    set_q(q_host);
+    const int W = multi_lanes();
+    if (W < 2 || nrhs == 1) {  // one at a time through the single solve
+        for (int64_t c = 0; c < nrhs; ++c)
+            solve_cg(B + c * ld, nullptr, imax, eps, X_out + c * ld, trace_out ? trace_out + c * (imax + 1) : nullptr,
+                     iters ? iters + c : nullptr);
+        return;
+    }
+    cg_active = false;  // the group borrows sc, red, raw and the slab of the single solve
+    for (int64_t c0 = 0; c0 < nrhs; c0 += W)
+        solve_cg_group(B + c0 * ld, (int) std::min<int64_t>(W, nrhs - c0), ld, imax, eps, X_out + c0 * ld,
+                       trace_out ? trace_out + c0 * (imax + 1) : nullptr, iters ? iters + c0 : nullptr);
+}
+
+// RET_c += add * Q~ P_c for nrhs columns (row c of P / RET at c * ld)
+template <typename T>
+void engine<T>::kp_multi(const T *q_host, const T *P, T *RET, int64_t nrhs, int64_t ld, T add) {
+    need_data();
+    if (nrhs < 1) throw mi_error(-1, "at least one vector is needed");
+    if (ld < m) throw mi_error(-1, "the leading dimension is smaller than the number of rows");
+    MI_HIP_CHECK(hipSetDevice(device));
+    const int W = nrhs == 1 ? 1 : multi_lanes();
+    if (W < 2) {
+        for (int64_t c = 0; c < nrhs; ++c) kp_host(q_host, P + c * ld, RET + c * ld, add);
+        return;
+    }
+    set_q(q_host);
+    cg_active = false;
+    for (int64_t c0 = 0; c0 < nrhs; c0 += W) {
+        const int nvec = (int) std::min<int64_t>(W, nrhs - c0);
+        MI_HIP_CHECK(hipMemsetAsync(lanes.sc.get(), 0, sizeof(cg_scalars<T>) * (size_t) nvec, stream));
+        for (int c = 0; c < nvec; ++c) {
+            MI_HIP_CHECK(hipMemcpyAsync(lane_v(LV_D, c), P + (c0 + c) * ld, sizeof(T) * (size_t) m, hipMemcpyHostToDevice, stream));
+            MI_HIP_CHECK(hipMemcpyAsync(lane_v(LV_R, c), RET + (c0 + c) * ld, sizeof(T) * (size_t) m, hipMemcpyHostToDevice, stream));
+        }
+        int first = 0;
+        if (kcache_tiles > 0 && !kcache_valid) {  // an unfilled tile cache: the first vector fills it, on the single path
+            MI_HIP_CHECK(hipMemsetAsync(sc.get(), 0, sizeof(cg_scalars<T>), stream));
+            kp_device(lane_v(LV_D, 0), lane_v(LV_R, 0), add, false, nullptr);
+            first = 1;
+        }
+        for (int c = first; c < nvec; ++c) {
+            launch_dot2<T>(lane_v(LV_D, c), nullptr, qf(), lane_v(LV_D, c), m, lane_red(c), nullptr, stream);
+            launch_dot_final<T>(lane_red(c), lanes.sc.get() + c, FIN_SP_SQP, 0, nullptr, 0, nullptr, stream, 1);
+        }
+        if (nvec > first) tiles_multi(LV_D, first, nvec - first, false);
+        for (int c = first; c < nvec; ++c) {
+            launch_kp_reduce<T>(lanes.slab.get() + (int64_t) c * lanes.sstride, nb, m, t0, t1, kp_wgoff.get(),
+                                lane_v(LV_RAW, c), nullptr, stream);
+            launch_kp_finalize<T>(lane_v(LV_RAW, c), qf(), lane_v(LV_D, c), lanes.sc.get() + c, QAf(), cost_inv(), add, 0, m,
+                                  lane_v(LV_R, c), nullptr, stream);
+        }
+        for (int c = 0; c < nvec; ++c)
+            MI_HIP_CHECK(hipMemcpyAsync(RET + (c0 + c) * ld, lane_v(LV_R, c), sizeof(T) * (size_t) m, hipMemcpyDeviceToHost, stream));
+        MI_HIP_CHECK(hipStreamSynchronize(stream));
+    }
+}
+
+// learn() per class of a one-vs-all label matrix Y[nclass][ldy] (+-1), the solves as one multi-right-hand-side CG
+template <typename T>
+void engine<T>::learn_multi(const T *Y, int64_t nclass, int64_t ldy, int64_t imax, T eps, T *alpha_out, double *bias_out,
+                            double *trace_out, int64_t *iters) {
+    need_data();
+    if (Y == nullptr) throw mi_error(-1, "No labels given for training! Maybe the data is only usable for prediction?");
+    if (nclass < 1) throw mi_error(-1, "at least one class is needed");
+    if (ldy < n) throw mi_error(-1, "the leading dimension is smaller than the number of points");
+    std::vector<T> qh(std::max<int64_t>(m, 1)), bh((size_t) (nclass * ldy));  // b rows ldy apart, like alpha_out's
+    generate_q(qh.data(), nullptr);
+    for (int64_t c = 0; c < nclass; ++c)
+        for (int64_t i = 0; i < m; ++i) bh[(size_t) (c * ldy + i)] = Y[c * ldy + i] - Y[c * ldy + m];  // b = y - y_m
+    if (imax < 0) imax = d;
+    solve_cg_multi(bh.data(), nclass, ldy, nullptr, imax, eps, alpha_out, trace_out, iters);
+    for (int64_t c = 0; c < nclass; ++c) {
+        const T *y = Y + c * ldy;
+        T *alpha = alpha_out + c * ldy;
+        T s = 0, qa = 0;
+        for (int64_t i = 0; i < m; ++i) s += alpha[i];
+        for (int64_t i = 0; i < m; ++i) qa = std::fma(qh[i], alpha[i], qa);
+        alpha[m] = -s;
+        if (bias_out) bias_out[c] = (double) (y[m] + QA_cost * s - qa);
+    }
+}
+
+// time_kp's K·p time for the batched product of nrhs resident vectors (groups of at most the width; one at a time
+// where nothing is batched): dots, tiles, reduce and finalize of every vector
+template <typename T>
+void engine<T>::time_kp_multi(int64_t nrhs, int reps, double *ms_kp) {
+    need_data();
+    need_q();
+    if (nrhs < 1) throw mi_error(-1, "at least one vector is needed");
+    MI_HIP_CHECK(hipSetDevice(device));
+    if (reps < 1) reps = 1;
+    const int W = multi_lanes();
+    cg_active = false;
+    std::vector<T> ph(std::max<int64_t>(m, 1));
+    for (int64_t i = 0; i < m; ++i) ph[i] = T(1) + T((i * 2654435761ull) % 1000) / T(1000);
+    T *p0 = W < 2 ? pv.get() : lane_v(LV_D, 0);
+    const int nl = W < 2 ? 1 : (int) std::min<int64_t>(W, nrhs);
+    for (int c = 0; c < nl; ++c)
+        if (m > 0) MI_HIP_CHECK(hipMemcpyAsync(W < 2 ? p0 : lane_v(LV_D, c), ph.data(), sizeof(T) * (size_t) m, hipMemcpyHostToDevice, stream));
+    MI_HIP_CHECK(hipMemsetAsync(sc.get(), 0, sizeof(cg_scalars<T>), stream));
+    if (W >= 2) MI_HIP_CHECK(hipMemsetAsync(lanes.sc.get(), 0, sizeof(cg_scalars<T>) * (size_t) W, stream));
+    kp_device(p0, ret.get(), T(1), true, nullptr);  // warm-up; fills an unfilled tile cache
+    auto product = [&]() {
+        if (W < 2) {
+            for (int64_t c = 0; c < nrhs; ++c) kp_device(p0, ret.get(), T(1), true, nullptr);
+            return;
+        }
+        for (int64_t c0 = 0; c0 < nrhs; c0 += W) {
+            const int nvec = (int) std::min<int64_t>(W, nrhs - c0);
+            for (int c = 0; c < nvec; ++c) {
+                launch_dot2<T>(lane_v(LV_D, c), nullptr, qf(), lane_v(LV_D, c), m, lane_red(c), nullptr, stream);
+                launch_dot_final<T>(lane_red(c), lanes.sc.get() + c, FIN_SP_SQP, 0, nullptr, 0, nullptr, stream, 1);
+            }
+            tiles_multi(LV_D, 0, nvec, false);
+            for (int c = 0; c < nvec; ++c) {
+                launch_kp_reduce<T>(lanes.slab.get() + (int64_t) c * lanes.sstride, nb, m, t0, t1, kp_wgoff.get(),
+                                    lane_v(LV_RAW, c), nullptr, stream);
+                launch_kp_finalize<T>(lane_v(LV_RAW, c), qf(), lane_v(LV_D, c), lanes.sc.get() + c, QAf(), cost_inv(), T(1), 1,
+                                      m, lane_v(LV_R, c), nullptr, stream);
+            }
+        }
+    };
+    product();  // warm-up
+    hipEvent_t e0, e1;
+    MI_HIP_CHECK(hipEventCreate(&e0));
+    MI_HIP_CHECK(hipEventCreate(&e1));
+    MI_HIP_CHECK(hipEventRecord(e0, stream));
+    for (int it = 0; it < reps; ++it) product();
+    MI_HIP_CHECK(hipEventRecord(e1, stream));
+    MI_HIP_CHECK(hipEventSynchronize(e1));
+    float ms = 0;
+    MI_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    (void) hipEventDestroy(e0);
+    (void) hipEventDestroy(e1);
+    if (ms_kp) *ms_kp = ms / reps;
+}
+
 template <typename T>
 int64_t engine<T>::device_bytes() const {
     return XT.bytes() + norms.bytes() + xlast.bytes() + partial.bytes() + kcache.bytes() + q.bytes() * 10 + w.bytes() +
-           csr_bytes();
+           csr_bytes() + lanes.bytes();
 }
 
 template struct engine<float>;

@@ -221,6 +221,47 @@ struct engine : engine_base {
     void learn(const T *y, int64_t imax, T eps, T *alpha_out, double *bias_out, double *trace_out, int64_t *iters);
     void time_kp(int reps, double *ms_kp, double *ms_dom);
 
+    // ---- several right-hand sides over one pass of the tiles ----
+    // The one-vs-all systems of a multi-class problem share Q~ and differ in b, so their CG solves run as lanes: a
+    // lane is one right-hand side's device state (x, r, d, Ad, b, raw, its partials, cg_scalars, trace and tile slab).
+    // Each iteration makes ONE pass over the tiles for the live lanes' direction vectors (launch_kp_tiles_multi) and
+    // then runs the single solve's own launches per lane on the lane's buffers, so every lane's x, trace and
+    // iteration count are bitwise solve_cg's on that right-hand side alone. The single-solve members above are not
+    // touched by a batched group except sc, red, raw and partial (the shared first product Q~ x0, x0 = 1).
+    // Batched: the pairwise tile path on one rank (multi_batched); everywhere else, and when not even two lanes fit
+    // in device memory, the same entry points run the right-hand sides one after another through solve_cg / kp_host.
+    struct lane_pool {
+        int width = 0;                     // lanes allocated: 0 = not yet, 1 = none fit (one at a time)
+        int64_t vstride = 0, sstride = 0;  // elements between two lanes' vectors / slabs
+        dev_buf<T> vec;                    // [LV_COUNT][width][vstride], zero padded like the engine's vectors
+        dev_buf<T> slab;                   // [width][sstride = kp_wgs * KP_REC]
+        dev_buf<T> part;                   // [width][8 RED_BLOCKS]: a lane's cgp (6 R), then its red (2 R)
+        dev_buf<cg_scalars<T>> sc;         // [width]
+        dev_buf<double> trace;             // [width][trace_cap]
+        int64_t trace_cap = 0;
+        int64_t bytes() const { return vec.bytes() + slab.bytes() + part.bytes() + sc.bytes() + trace.bytes(); }
+    };
+    enum lane_vec { LV_X = 0, LV_R, LV_D, LV_AD, LV_B, LV_RAW, LV_COUNT };
+    lane_pool lanes;
+    int multi_opt = 0;  // PLSSVM_MI_OPT_MULTI_WIDTH: 0 auto, 1 one at a time, n >= 2 at most n lanes
+    T *lane_v(int kind, int c) const { return lanes.vec.get() + ((int64_t) kind * lanes.width + c) * lanes.vstride; }
+    T *lane_cgp(int c) const { return lanes.part.get() + (int64_t) c * 8 * RED_BLOCKS; }
+    T *lane_red(int c) const { return lane_cgp(c) + 6 * RED_BLOCKS; }
+    bool multi_batched() const;           // this setup runs the batched path (given memory for two lanes)
+    int64_t lane_bytes() const;           // device memory of one lane
+    int multi_width_next() const;         // the width the next multi call would use (1: one at a time); allocates nothing
+    int multi_lanes();                    // the lanes, allocated at the first call (width halved until it fits)
+    void tiles_multi(int kind, int c0, int nvec, bool flags);  // one pass over the tiles for lanes [c0, c0 + nvec)
+    void multi_first_product(int c);      // Q~ x0 of a group, through the single-vector path (fills the tile cache)
+    void cg_iter_multi(int nvec, int reset);
+    void solve_cg_group(const T *B, int nvec, int64_t ld, int64_t imax, T eps, T *X_out, double *trace_out, int64_t *iters);
+    void solve_cg_multi(const T *B, int64_t nrhs, int64_t ld, const T *q_host, int64_t imax, T eps, T *X_out,
+                        double *trace_out, int64_t *iters);
+    void kp_multi(const T *q_host, const T *P, T *RET, int64_t nrhs, int64_t ld, T add);
+    void learn_multi(const T *Y, int64_t nclass, int64_t ldy, int64_t imax, T eps, T *alpha_out, double *bias_out,
+                     double *trace_out, int64_t *iters);
+    void time_kp_multi(int64_t nrhs, int reps, double *ms_kp);
+
     // sparse paths (sparse.hip)
     void sparse_q();                                              // q, norms, e on CSR data
     void build_gram_blocks(const int64_t *cpos, int64_t max_inc);  // sparse Gram pattern (pairwise kernels)

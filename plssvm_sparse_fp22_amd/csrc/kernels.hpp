@@ -75,6 +75,18 @@ void launch_kp_tiles(kfun<T> kf, const T *XT, const T *norms, const T *p, T *par
                      const cg_scalars<T> *status, hipStream_t s, T *kcache = nullptr, int64_t cached = 0,
                      bool fill = false);
 
+// The same tiles for nvec vectors at once (2 .. KP_MULTI_W; 1 is legal): vector c is p + c * pstride, its slab
+// partial + c * sstride, its stop flag status[c] (status null: none; a vector whose flag says converged is skipped and
+// its slab left alone). A tile's kernel values are formed or streamed once per visit and multiplied with every
+// vector in the single-vector kernel's order: slab c is bitwise launch_kp_tiles' slab for p_c. Tiles [0, cached) are
+// streamed from kcache, whose records must be filled (launch_kp_tiles with fill), the rest are computed.
+constexpr int KP_MULTI_W = 8;
+template <typename T>
+void launch_kp_tiles_multi(kfun<T> kf, const T *XT, const T *norms, const T *p, int64_t pstride, T *partial,
+                           int64_t sstride, int nvec, int64_t n_pad, int64_t d_pad, int64_t nb, int64_t s0,
+                           int64_t nsuper, const int32_t *wg_off, int64_t wgs, const cg_scalars<T> *status, hipStream_t s,
+                           const T *kcache = nullptr, int64_t cached = 0);
+
 // raw[i] = sum over the column blocks c in order of row i's slab values of the tiles whose super-block lies
 // in [s0, s1) (tile (Ib, c) row sums for c <= Ib, tile (c, Ib) column sums for c > Ib); i < m
 template <typename T>

@@ -163,8 +163,16 @@ constexpr bool kp_dma_after_reads() {
 #ifndef KP_LOAD_WAVES
 #define KP_LOAD_WAVES 0
 #endif
-template <typename T, int KERNEL, int MODE>
+// The multi-vector KP_LOAD keeps the whole record live across the loop over vectors: in fp64 that does not fit 168
+// VGPRs (22 spilled dwords, three of them record chunks whose spill stores wait for their loads right after issue,
+// which serialises the head of the stream), so it runs 2 workgroups per CU with 256 VGPRs; KP_MULTI_LOAD_WAVES=3
+// builds the 3-per-CU variant (A/B in DESIGN.md §3.1.3)
+#ifndef KP_MULTI_LOAD_WAVES
+#define KP_MULTI_LOAD_WAVES 2
+#endif
+template <typename T, int KERNEL, int MODE, bool MULTI = false>
 constexpr int kp_mode_waves() {
+    if (MULTI && MODE == KP_LOAD && sizeof(T) == 8) return KP_MULTI_LOAD_WAVES;
     if (MODE != KP_LOAD) return kp_waves_per_eu<T, KERNEL>();
     return KP_LOAD_WAVES > 0 ? KP_LOAD_WAVES : (sizeof(T) == 8 ? 3 : 4);
 }
@@ -185,14 +193,25 @@ struct kp_vec<float> {
 // on — the same fma order, LDS park and sums, so the slab record is bitwise the computed one. A cache record is
 // in register layout, [value group][thread][VEC]: a lane's 64 values in (mt, r, nt) order, 16 bytes per lane and
 // group, so every wave-instruction moves one contiguous KiB. wg_base: the first workgroup (tile) of this launch.
-template <typename T, int KERNEL, int MODE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_waves<T, KERNEL, MODE>(), kp_mode_waves<T, KERNEL, MODE>()))) void kp_tile_kernel(kfun<T> kf, const T *__restrict__ XT,
+//
+// MULTI: nvec (<= KP_MULTI_W) vectors per visit of a tile (the single-vector instances ignore nvec and the
+// strides). Vector c is p + c * pstride, its slab partial + c * sstride, its stop flag status[c]. The tile's kernel
+// values are formed (or loaded) once and stay in the accumulator registers; the "times p" epilogue then runs once per
+// vector with that vector's p_I / p_J staged in LDS, in the single-vector kernel's fma, park and summation order:
+// slab c is bitwise the slab the single-vector kernel writes for p_c. A vector whose flag says converged is skipped
+// (its slab is left alone). Every MULTI statement sits in an `if constexpr`, and the MULTI epilogue is written out
+// beside the single one instead of sharing a helper with it: the single-vector instances must keep their registers,
+// scratch and LDS (a shared body or lambda moved them).
+template <typename T, int KERNEL, int MODE, bool MULTI = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_waves<T, KERNEL, MODE, MULTI>(), kp_mode_waves<T, KERNEL, MODE, MULTI>()))) void kp_tile_kernel(kfun<T> kf, const T *__restrict__ XT,
                                                          const T *__restrict__ norms, const T *__restrict__ p,
                                                          T *__restrict__ partial, int64_t n_pad, int64_t d_pad,
                                                          int64_t nb, int64_t s0, int64_t nsuper,
                                                          const int32_t *__restrict__ wg_off,
                                                          const cg_scalars<T> *__restrict__ status, int64_t wg_base,
-                                                         T *__restrict__ kcache) {
+                                                         T *__restrict__ kcache, int nvec, int64_t pstride,
+                                                         int64_t sstride) {
+    static_assert(!MULTI || MODE != KP_COMPUTE_STORE, "the tile cache is filled by the single-vector kernel");
     using M = mfma16<T>;
     using acc_t = typename M::acc_t;
     using vec_t = typename kp_vec<T>::type;
@@ -213,7 +232,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_wav
     constexpr int NGRP = 64 / VEC;  // 16-byte groups of a lane's 64 values
     __shared__ double exp_tab[FAST_EXP ? EXP_TAB : 1];
 
-    if (status != nullptr && status->converged) return;
+    unsigned live = 1;  // MULTI: bit c = vector c is still iterating
+    if constexpr (MULTI) {
+        live = 0;
+        for (int c = 0; c < nvec; ++c)
+            if (status == nullptr || !status[c].converged) live |= 1u << c;
+        if (live == 0) return;
+    } else {
+        if (status != nullptr && status->converged) return;
+    }
 
     // workgroups: one per real tile. wg_off[k] = first workgroup of the rank's super-block s0 + k (a full
     // super-block has 64 tiles, a diagonal one 36, the ragged last super-block row fewer): no empty
@@ -256,11 +283,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_wav
         const vec_t *rec = reinterpret_cast<const vec_t *>(kcache + wg * KP_CACHE_REC) + tid;
 #pragma unroll
         for (int g = 0; g < NGRP; ++g) kld[g] = rec[g * 256];
-        smem[tid] = p[pidx];
-        __syncthreads();  // p_I, p_J visible
+        if constexpr (!MULTI) {
+            smem[tid] = p[pidx];
+            __syncthreads();  // p_I, p_J visible
+        }
     } else {
         // p and norms of the tile's rows/cols -> LDS (issued first: their wait must not drain the DMA)
-        const T pin = p[pidx];
+        const T pin = MULTI ? T(0) : p[pidx];  // MULTI stages each vector's p after the K loop
         const T nin = (KERNEL == 2) ? norms[pidx] : T(0);
         // fast fp64 RBF: the accumulators start at -n_j / 2 (column j = lane & 15 of every block), so they
         // end at g_ij - n_j / 2 and y_ij = 2 g KEXP (g_ij - n_j / 2) - g KEXP n_i is one fma per element
@@ -300,7 +329,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_wav
 
         issue(0, 0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        smem[tid] = pin;
+        if constexpr (!MULTI) smem[tid] = pin;
         smem[2 * KP_TILE + tid] = nin;
         if constexpr (FAST_EXP) {
             if (tid < EXP_TAB) exp_tab[tid] = c_exp2_256[tid];  // visible after the first K-loop barrier
@@ -337,77 +366,162 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_wav
     }
 
     // ---- epilogue: kernel function, times p, row and column partial sums ----
-    const T *pI = smem, *pJ = smem + KP_TILE, *nI = smem + 2 * KP_TILE, *nJ = smem + 3 * KP_TILE;
-    T pj[4], nj[4];
+    if constexpr (!MULTI) {
+        const T *pI = smem, *pJ = smem + KP_TILE, *nI = smem + 2 * KP_TILE, *nJ = smem + 3 * KP_TILE;
+        T pj[4], nj[4];
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-        const int jl = wc * 64 + nt * 16 + (lane & 15);
-        pj[nt] = pJ[jl];
-        nj[nt] = (KERNEL == 2 && !FAST_EXP) ? nJ[jl] : T(0);
-    }
-    T cs[4] = { 0, 0, 0, 0 };
-    const T c2 = FAST_EXP ? T(2) * kf.gamma * T(KEXP) : T(0);
-    // Each row has 32 partials (16 lanes x 2 column-half waves), each column 8 (4 lane groups x 2
-    // row-half waves). They are parked in LDS and every thread then sums one half-row and one
-    // half-column: ~20 adds per lane instead of a 4-level shuffle tree per row (64 adds + 128
-    // ds_bpermute); the fixed summation order keeps K·p bitwise reproducible.
-    __syncthreads();  // every wave is done with the last K chunk: the panels become reduction buffers
-    T *rowp = smem + OFF_PAN + wc * RHALF;
+        for (int nt = 0; nt < 4; ++nt) {
+            const int jl = wc * 64 + nt * 16 + (lane & 15);
+            pj[nt] = pJ[jl];
+            nj[nt] = (KERNEL == 2 && !FAST_EXP) ? nJ[jl] : T(0);
+        }
+        T cs[4] = { 0, 0, 0, 0 };
+        const T c2 = FAST_EXP ? T(2) * kf.gamma * T(KEXP) : T(0);
+        // Each row has 32 partials (16 lanes x 2 column-half waves), each column 8 (4 lane groups x 2
+        // row-half waves). They are parked in LDS and every thread then sums one half-row and one
+        // half-column: ~20 adds per lane instead of a 4-level shuffle tree per row (64 adds + 128
+        // ds_bpermute); the fixed summation order keeps K·p bitwise reproducible.
+        __syncthreads();  // every wave is done with the last K chunk: the panels become reduction buffers
+        T *rowp = smem + OFF_PAN + wc * RHALF;
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
+        for (int mt = 0; mt < 4; ++mt) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int il = wr * 64 + mt * 16 + M::row(lane, r);
-            const T pi = pI[il];
-            const T ni = MODE == KP_LOAD ? T(0) : nI[il];
-            const T ai = FAST_EXP ? -kf.gamma * T(KEXP) * ni : T(0);
-            T s = 0;
-            T kvs[4];
+            for (int r = 0; r < 4; ++r) {
+                const int il = wr * 64 + mt * 16 + M::row(lane, r);
+                const T pi = pI[il];
+                const T ni = MODE == KP_LOAD ? T(0) : nI[il];
+                const T ai = FAST_EXP ? -kf.gamma * T(KEXP) * ni : T(0);
+                T s = 0;
+                T kvs[4];
 #pragma unroll
-            for (int nt = 0; nt < 4; ++nt) {
-                T kv;
-                if constexpr (MODE == KP_LOAD)
-                    kv = kld[((mt * 4 + r) * 4 + nt) / VEC][nt % VEC];
-                else if constexpr (FAST_EXP)
-                    kv = (T) exp_scaled_f64(fma(c2, acc[mt][nt][r], ai), exp_tab);
-                else
-                    kv = kernel_apply<T>(KERNEL, kf.degree, kf.gamma, kf.coef0, acc[mt][nt][r], ni, nj[nt]);
-                kvs[nt] = kv;
-                s = fma(kv, pj[nt], s);
-                cs[nt] = fma(kv, pi, cs[nt]);
-            }
-            rowp[il * RSTR + (lane & 15)] = s;
-            if constexpr (MODE == KP_COMPUTE_STORE) {
-                vec_t *rec = reinterpret_cast<vec_t *>(kcache + wg * KP_CACHE_REC) + tid;
+                for (int nt = 0; nt < 4; ++nt) {
+                    T kv;
+                    if constexpr (MODE == KP_LOAD)
+                        kv = kld[((mt * 4 + r) * 4 + nt) / VEC][nt % VEC];
+                    else if constexpr (FAST_EXP)
+                        kv = (T) exp_scaled_f64(fma(c2, acc[mt][nt][r], ai), exp_tab);
+                    else
+                        kv = kernel_apply<T>(KERNEL, kf.degree, kf.gamma, kf.coef0, acc[mt][nt][r], ni, nj[nt]);
+                    kvs[nt] = kv;
+                    s = fma(kv, pj[nt], s);
+                    cs[nt] = fma(kv, pi, cs[nt]);
+                }
+                rowp[il * RSTR + (lane & 15)] = s;
+                if constexpr (MODE == KP_COMPUTE_STORE) {
+                    vec_t *rec = reinterpret_cast<vec_t *>(kcache + wg * KP_CACHE_REC) + tid;
 #pragma unroll
-                for (int h = 0; h < 4 / VEC; ++h) {
-                    vec_t v;
+                    for (int h = 0; h < 4 / VEC; ++h) {
+                        vec_t v;
 #pragma unroll
-                    for (int e = 0; e < VEC; ++e) v[e] = kvs[h * VEC + e];
-                    rec[((mt * 4 + r) * (4 / VEC) + h) * 256] = v;
+                        for (int e = 0; e < VEC; ++e) v[e] = kvs[h * VEC + e];
+                        rec[((mt * 4 + r) * (4 / VEC) + h) * 256] = v;
+                    }
                 }
             }
         }
-    }
-    if (!diag) {
-        T *colp = smem + OFF_PAN + 2 * RHALF + wr * KP_TILE * CSTR;
+        if (!diag) {
+            T *colp = smem + OFF_PAN + 2 * RHALF + wr * KP_TILE * CSTR;
 #pragma unroll
-        for (int nt = 0; nt < 4; ++nt) colp[(wc * 64 + nt * 16 + (lane & 15)) * CSTR + (lane >> 4)] = cs[nt];
-    }
-    __syncthreads();
-    const int q = tid >> 1, h = tid & 1;  // row / column q of the tile, half h
-    const T *rp = smem + OFF_PAN + h * RHALF + q * RSTR;
-    T a = rp[0];
+            for (int nt = 0; nt < 4; ++nt) colp[(wc * 64 + nt * 16 + (lane & 15)) * CSTR + (lane >> 4)] = cs[nt];
+        }
+        __syncthreads();
+        const int q = tid >> 1, h = tid & 1;  // row / column q of the tile, half h
+        const T *rp = smem + OFF_PAN + h * RHALF + q * RSTR;
+        T a = rp[0];
 #pragma unroll
-    for (int k = 1; k < 16; ++k) a += rp[k];
-    a += __shfl_xor(a, 1);
-    if (!diag) {
-        const T *cp = smem + OFF_PAN + 2 * RHALF + (h * KP_TILE + q) * CSTR;
-        T c = (cp[0] + cp[1]) + (cp[2] + cp[3]);
-        c += __shfl_xor(c, 1);
-        if (h == 1) partial[wg * KP_REC + KP_TILE + q] = c;  // column sums of the J rows
+        for (int k = 1; k < 16; ++k) a += rp[k];
+        a += __shfl_xor(a, 1);
+        if (!diag) {
+            const T *cp = smem + OFF_PAN + 2 * RHALF + (h * KP_TILE + q) * CSTR;
+            T c = (cp[0] + cp[1]) + (cp[2] + cp[3]);
+            c += __shfl_xor(c, 1);
+            if (h == 1) partial[wg * KP_REC + KP_TILE + q] = c;  // column sums of the J rows
+        }
+        if (h == 0) partial[wg * KP_REC + q] = a;  // row sums of the I rows
+    } else {
+        // The same epilogue in two steps. First the kernel function, once, in place: the call and its arguments are
+        // the single-vector branch's, so the values are its values (KP_LOAD: they are the record). Then one turn per
+        // live vector: its p_I / p_J staged where the single-vector kernel keeps them (LDS keeps its size for any
+        // nvec), its fma chains, park and sums in the order above, its record of slab c.
+        const T *pI = smem, *pJ = smem + KP_TILE, *nI = smem + 2 * KP_TILE, *nJ = smem + 3 * KP_TILE;
+        if constexpr (MODE != KP_LOAD) {
+            T nj[4];
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) nj[nt] = (KERNEL == 2 && !FAST_EXP) ? nJ[wc * 64 + nt * 16 + (lane & 15)] : T(0);
+            const T c2 = FAST_EXP ? T(2) * kf.gamma * T(KEXP) : T(0);
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const T ni = nI[wr * 64 + mt * 16 + M::row(lane, r)];
+                    const T ai = FAST_EXP ? -kf.gamma * T(KEXP) * ni : T(0);
+#pragma unroll
+                    for (int nt = 0; nt < 4; ++nt) {
+                        if constexpr (FAST_EXP)
+                            acc[mt][nt][r] = (T) exp_scaled_f64(fma(c2, acc[mt][nt][r], ai), exp_tab);
+                        else
+                            acc[mt][nt][r] = kernel_apply<T>(KERNEL, kf.degree, kf.gamma, kf.coef0, acc[mt][nt][r], ni, nj[nt]);
+                    }
+                }
+            }
+        }
+        T *rowp = smem + OFF_PAN + wc * RHALF;
+        const int q = tid >> 1, h = tid & 1;  // row / column q of the tile, half h
+        int c = __builtin_ctz(live);
+        T pnext = p[c * pstride + pidx];  // the next live vector's element is fetched while this one is multiplied
+        while (true) {
+            smem[tid] = pnext;  // the previous turn's reads of p_I / p_J lie before its second barrier
+            __syncthreads();    // p_c visible; every wave is done with the last K chunk / the previous turn's sums
+            const unsigned rest = live >> (c + 1);
+            const int cn = rest != 0 ? c + 1 + __builtin_ctz(rest) : -1;
+            if (cn >= 0) pnext = p[cn * pstride + pidx];
+            T pj[4];
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) pj[nt] = pJ[wc * 64 + nt * 16 + (lane & 15)];
+            T cs[4] = { 0, 0, 0, 0 };
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int il = wr * 64 + mt * 16 + M::row(lane, r);
+                    const T pi = pI[il];
+                    T s = 0;
+#pragma unroll
+                    for (int nt = 0; nt < 4; ++nt) {
+                        T kv;
+                        if constexpr (MODE == KP_LOAD)
+                            kv = kld[((mt * 4 + r) * 4 + nt) / VEC][nt % VEC];
+                        else
+                            kv = acc[mt][nt][r];
+                        s = fma(kv, pj[nt], s);
+                        cs[nt] = fma(kv, pi, cs[nt]);
+                    }
+                    rowp[il * RSTR + (lane & 15)] = s;
+                }
+            }
+            if (!diag) {
+                T *colp = smem + OFF_PAN + 2 * RHALF + wr * KP_TILE * CSTR;
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) colp[(wc * 64 + nt * 16 + (lane & 15)) * CSTR + (lane >> 4)] = cs[nt];
+            }
+            __syncthreads();
+            T *slab = partial + c * sstride;
+            const T *rp = smem + OFF_PAN + h * RHALF + q * RSTR;
+            T a = rp[0];
+#pragma unroll
+            for (int k = 1; k < 16; ++k) a += rp[k];
+            a += __shfl_xor(a, 1);
+            if (!diag) {
+                const T *cp = smem + OFF_PAN + 2 * RHALF + (h * KP_TILE + q) * CSTR;
+                T cc = (cp[0] + cp[1]) + (cp[2] + cp[3]);
+                cc += __shfl_xor(cc, 1);
+                if (h == 1) slab[wg * KP_REC + KP_TILE + q] = cc;  // column sums of the J rows
+            }
+            if (h == 0) slab[wg * KP_REC + q] = a;  // row sums of the I rows
+            if (cn < 0) break;
+            c = cn;
+        }
     }
-    if (h == 0) partial[wg * KP_REC + q] = a;  // row sums of the I rows
 }
 
 // Slab values of row i (row block Ib, offset q) for the column blocks c of column super-block CS, in c
@@ -490,7 +604,7 @@ void launch_kp_mode(kfun<T> kf, const T *XT, const T *norms, const T *p, T *part
     const dim3 grid((unsigned) count), block(256);
 #define KP_LAUNCH(KERNEL)                                                                                         \
     hipLaunchKernelGGL((kp_tile_kernel<T, KERNEL, MODE>), grid, block, 0, s, kf, XT, norms, p, partial, n_pad, d_pad, \
-                       nb, s0, nsuper, wg_off, status, base, kcache)
+                       nb, s0, nsuper, wg_off, status, base, kcache, 1, (int64_t) 0, (int64_t) 0)
     if constexpr (MODE == KP_LOAD) {
         KP_LAUNCH(0);  // one instance per real type: the stored values are past the kernel function
     } else {
@@ -529,6 +643,40 @@ void launch_kp_tiles(kfun<T> kf, const T *XT, const T *norms, const T *p, T *par
                                   status, nullptr, s);
 }
 
+// The batched form: nvec vectors p + c * pstride into the slabs partial + c * sstride, stop flags status[c] (null:
+// none). The cached prefix must be filled already (the single-vector path's first K·p does that): tiles [0, cached)
+// are streamed, the rest computed, each once for all vectors.
+template <typename T>
+void launch_kp_tiles_multi(kfun<T> kf, const T *XT, const T *norms, const T *p, int64_t pstride, T *partial,
+                           int64_t sstride, int nvec, int64_t n_pad, int64_t d_pad, int64_t nb, int64_t s0,
+                           int64_t nsuper, const int32_t *wg_off, int64_t wgs, const cg_scalars<T> *status, hipStream_t s,
+                           const T *kcache, int64_t cached) {
+    if (nsuper <= 0 || nb <= 0 || wgs <= 0) return;
+    if (nvec < 1 || nvec > KP_MULTI_W) throw mi_error(-1, "bad vector count for the batched tile kernel");
+    if ((int64_t) kp_dpad<T>() * n_pad * (int64_t) sizeof(T) >= ((int64_t) 1 << 31))
+        throw mi_error(-5, "too many points for the pairwise tile kernel's 32-bit chunk offsets");
+    if (kcache == nullptr || cached < 0) cached = 0;
+    if (cached > wgs) cached = wgs;
+    const dim3 block(256);
+#define KP_LAUNCH(KERNEL, MODE, base, count)                                                                          \
+    hipLaunchKernelGGL((kp_tile_kernel<T, KERNEL, MODE, true>), dim3((unsigned) (count)), block, 0, s, kf, XT, norms, p, \
+                       partial, n_pad, d_pad, nb, s0, nsuper, wg_off, status, (int64_t) (base), const_cast<T *>(kcache),  \
+                       nvec, pstride, sstride)
+    if (cached > 0) {
+        KP_LAUNCH(0, KP_LOAD, 0, cached);
+        MI_LAUNCH_CHECK();
+    }
+    if (wgs > cached) {
+        switch (kf.kernel) {
+            case 0: KP_LAUNCH(0, KP_COMPUTE, cached, wgs - cached); break;
+            case 1: KP_LAUNCH(1, KP_COMPUTE, cached, wgs - cached); break;
+            default: KP_LAUNCH(2, KP_COMPUTE, cached, wgs - cached); break;
+        }
+        MI_LAUNCH_CHECK();
+    }
+#undef KP_LAUNCH
+}
+
 // Both the whole triangle and a rank's share use the wave-split reduction (16 waves per 64 rows, each a
 // range of column super-blocks, partial sums added in wave order): one thread per row walking all nb
 // records (round 1's kp_reduce_kernel) was latency-bound — 0.43 ms for config 2's 627 MB slab.
@@ -545,6 +693,9 @@ void launch_kp_reduce(const T *partial, int64_t nb, int64_t m, int64_t s0, int64
     template void launch_kp_tiles<T>(kfun<T>, const T *, const T *, const T *, T *, int64_t, int64_t, int64_t, \
                                      int64_t, int64_t, const int32_t *, int64_t, const cg_scalars<T> *,        \
                                      hipStream_t, T *, int64_t, bool);                                          \
+    template void launch_kp_tiles_multi<T>(kfun<T>, const T *, const T *, const T *, int64_t, T *, int64_t, int,  \
+                                           int64_t, int64_t, int64_t, int64_t, int64_t, const int32_t *, int64_t,  \
+                                           const cg_scalars<T> *, hipStream_t, const T *, int64_t);               \
     template void launch_kp_reduce<T>(const T *, int64_t, int64_t, int64_t, int64_t, const int32_t *, T *,     \
                                       const cg_scalars<T> *, hipStream_t);
 INST(float)
