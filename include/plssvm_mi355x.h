@@ -119,6 +119,13 @@ extern "C" {
  * right-hand sides than the width run in groups, in order. plssvm_mi_info.multi_width reports the width in use. */
 #define PLSSVM_MI_OPT_MULTI_WIDTH 7
 
+/* 7-byte records for stored fp64 tiles: a 128 x 128 tile whose values are all positive normal numbers within 16
+ * binades (any RBF tile unless gamma is large) is kept as 52 mantissa bits + a 4-bit exponent offset per value below a
+ * per-tile base exponent, 112 KiB instead of 128 KiB, and decoded bit-exactly while it is streamed; every other tile
+ * (signs, zeros, denormals, inf, NaN, a wider span) and every fp32 tile keeps its raw record. Results are bitwise the
+ * same either way. 0 = auto (on), 1 = off. Environment PLSSVM_MI_KP_PACK=0, read at setup, also turns it off. */
+#define PLSSVM_MI_OPT_KP_PACK 8
+
 typedef struct plssvm_mi_ctx plssvm_mi_ctx;
 
 /* Number of visible HIP devices (>= 0), or a negative error code. */
@@ -344,6 +351,9 @@ typedef struct {
     int64_t kp_cache_bytes; /* device bytes of those records (tile_rows x tile_cols reals each) */
     int multi_width;        /* vectors the next multi-right-hand-side call serves per pass over the tiles
                                (PLSSVM_MI_OPT_MULTI_WIDTH); 1 = not batched: one vector at a time */
+    int64_t kp_cache_packed_tiles; /* of kp_cache_tiles: tiles stored at 7 bytes per value (PLSSVM_MI_OPT_KP_PACK);
+                                      0 before the first K·p of a setup has filled the cache; read back from the
+                                      device on the first request after that */
 } plssvm_mi_info;
 PLSSVM_MI_API int plssvm_mi_get_info(const plssvm_mi_ctx *ctx, plssvm_mi_info *info);
 

@@ -185,7 +185,7 @@ class CSVM:
 
     def __init__(self, params: Parameter, device=0, rank=0, world_size=1, uid=None, kp_mode="auto",
                  sim_rank=None, rbf_form=0, exchange=None, sparse_algo="auto", cg_variant=None, kp_cache=None,
-                 multi_width=None):
+                 multi_width=None, kp_pack=None):
         if params.data is None and params.csr is None and params.coo is None:
             raise ValueError("No data points provided!")
         if params.data is not None:
@@ -216,6 +216,8 @@ class CSVM:
             self._check(L.plssvm_mi_set_option(self._ctx, _abi.OPT_CG_VARIANT, v))
         if kp_cache is not None:  # False: never store kernel-matrix tiles, see PLSSVM_MI_OPT_KP_CACHE
             self._check(L.plssvm_mi_set_option(self._ctx, _abi.OPT_KP_CACHE, 0 if kp_cache else 1))
+        if kp_pack is not None:  # False: stored fp64 tiles keep their raw 8-byte records, see PLSSVM_MI_OPT_KP_PACK
+            self._check(L.plssvm_mi_set_option(self._ctx, _abi.OPT_KP_PACK, 0 if kp_pack else 1))
         if multi_width is not None:  # 0 auto, 1 one vector at a time, n: at most n lanes, see PLSSVM_MI_OPT_MULTI_WIDTH
             self._check(L.plssvm_mi_set_option(self._ctx, _abi.OPT_MULTI_WIDTH, int(multi_width)))
         if sim_rank is not None:  # (rank, world): single-GPU test hook, see PLSSVM_MI_OPT_SIM_RANK

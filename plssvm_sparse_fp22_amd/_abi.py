@@ -40,6 +40,7 @@ OPT_SPARSE_ALGO = 4
 OPT_CG_VARIANT = 5
 OPT_KP_CACHE = 6
 OPT_MULTI_WIDTH = 7
+OPT_KP_PACK = 8
 SPARSE_AUTO, SPARSE_PATTERN, SPARSE_EXPANSION, SPARSE_DENSE, SPARSE_ONTHEFLY = 0, 1, 2, 3, 4
 PART_KERNEL, PART_OVERLAP, PART_REMAINDER = 0, 1, 2
 XCHG_ALLREDUCE, XCHG_ALLGATHER = 0, 1
@@ -60,7 +61,7 @@ class Info(ctypes.Structure):
                 ("exp_waves", ctypes.c_int), ("exp_chunks", ctypes.c_int64), ("exp_hbytes", ctypes.c_int),
                 ("exp_layout", ctypes.c_int), ("exp_dot2", ctypes.c_int), ("centered", ctypes.c_int),
                 ("exp_lt", ctypes.c_int), ("kp_cache_tiles", ctypes.c_int64), ("kp_cache_bytes", ctypes.c_int64),
-                ("multi_width", ctypes.c_int)]
+                ("multi_width", ctypes.c_int), ("kp_cache_packed_tiles", ctypes.c_int64)]
 
 
 class BackendError(RuntimeError):

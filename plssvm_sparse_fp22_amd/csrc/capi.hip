@@ -115,6 +115,8 @@ int plssvm_mi_set_option(plssvm_mi_ctx *ctx, int key, int64_t value) {
             e.cg_variant = (int) value;
         } else if (key == PLSSVM_MI_OPT_KP_CACHE && value >= 0 && value <= 1) {
             e.kp_cache_opt = (int) value;
+        } else if (key == PLSSVM_MI_OPT_KP_PACK && value >= 0 && value <= 1) {
+            e.kp_pack_opt = (int) value;
         } else if (key == PLSSVM_MI_OPT_MULTI_WIDTH && value >= 0 && value <= 1024) {
             e.multi_opt = (int) value;
         } else {
@@ -446,6 +448,7 @@ int plssvm_mi_get_info(const plssvm_mi_ctx *cctx, plssvm_mi_info *info) {
         info->kp_cache_tiles = e.kcache_tiles;
         info->kp_cache_bytes = e.kcache.bytes();
         info->multi_width = e.multi_width_next();
+        info->kp_cache_packed_tiles = e.kcache_packed();
     });
 }
 

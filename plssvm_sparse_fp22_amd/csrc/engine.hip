@@ -106,6 +106,7 @@ engine<T>::~engine() {
     XT.reset();
     partial.reset();
     kcache.reset();
+    kdesc.reset();
     if (stream) (void) hipStreamDestroy(stream);
 }
 
@@ -432,6 +433,9 @@ void engine<T>::kcache_setup() {
     kcache_valid = false;
     kcache_tiles = 0;
     kcache.reset();
+    kdesc.reset();
+    kpack_on = false;
+    kpacked_host = -1;
     const bool tiles_path = !factored() && (!sparse || csr.dense_on);  // kp_raw's launch_kp_tiles branch
     const char *ke = std::getenv("PLSSVM_MI_KP_CACHE");
     if (!tiles_path || kp_cache_opt == 1 || (ke != nullptr && std::atoi(ke) == 0) || kp_wgs <= 0 || m <= 0) return;
@@ -441,12 +445,16 @@ void engine<T>::kcache_setup() {
     if (tiles <= 0) return;
     try {
         kcache.alloc(tiles * KP_CACHE_REC, stream, false);
+        kdesc.alloc(tiles + 1, stream);  // every tile raw, no tile packed; outside the budget: T does not depend on it
     } catch (const mi_error &) {
         (void) hipGetLastError();
         kcache.reset();
+        kdesc.reset();
         return;
     }
     kcache_tiles = tiles;
+    const char *pe = std::getenv("PLSSVM_MI_KP_PACK");
+    kpack_on = sizeof(T) == 8 && kp_pack_opt != 1 && !(pe != nullptr && std::atoi(pe) == 0);
     pt.mark("kp cache alloc");
 }
 
@@ -463,8 +471,22 @@ void engine<T>::kp_tiles_now(const T *p, const cg_scalars<T> *status) {
     }
     const int64_t cached = (kcache_valid || fill) ? kcache_tiles : 0;
     launch_kp_tiles<T>(kf(), XT.get(), norms.get(), p, partial.get(), n_pad, d_pad, nb, t0, t1 - t0, kp_wgoff.get(), kp_wgs,
-                       status, stream, kcache.get(), cached, fill);
+                       status, stream, kcache.get(), cached, fill, kdesc.get(), kdesc.get() + kcache_tiles, kpack_on);
     if (fill) kcache_valid = true;
+}
+
+// Tiles of the cache stored in the 7-byte form: the fill's counter, copied back once, on the first request after it
+template <typename T>
+int64_t engine<T>::kcache_packed() {
+    if (!kcache_valid || kcache_tiles <= 0 || !kpack_on) return 0;
+    if (kpacked_host < 0) {
+        int32_t c = 0;
+        MI_HIP_CHECK(hipSetDevice(device));
+        MI_HIP_CHECK(hipMemcpyAsync(&c, kdesc.get() + kcache_tiles, sizeof(c), hipMemcpyDeviceToHost, stream));
+        MI_HIP_CHECK(hipStreamSynchronize(stream));
+        kpacked_host = c;
+    }
+    return kpacked_host;
 }
 
 template <typename T>
@@ -1059,7 +1081,7 @@ void engine<T>::tiles_multi(int kind, int c0, int nvec, bool flags) {
     launch_kp_tiles_multi<T>(kf(), XT.get(), norms.get(), lane_v(kind, c0), lanes.vstride,
                              lanes.slab.get() + (int64_t) c0 * lanes.sstride, lanes.sstride, nvec, n_pad, d_pad, nb, t0,
                              t1 - t0, kp_wgoff.get(), kp_wgs, flags ? lanes.sc.get() + c0 : nullptr, stream, kcache.get(),
-                             kcache_valid ? kcache_tiles : 0);
+                             kcache_valid ? kcache_tiles : 0, kdesc.get());
 }
 
 // kp_device's first half for p = lane c's x0 = 1 on the engine's own buffers: sum p, sum q p in sc, the pairwise
@@ -1319,7 +1341,7 @@ void engine<T>::time_kp_multi(int64_t nrhs, int reps, double *ms_kp) {
 
 template <typename T>
 int64_t engine<T>::device_bytes() const {
-    return XT.bytes() + norms.bytes() + xlast.bytes() + partial.bytes() + kcache.bytes() + q.bytes() * 10 + w.bytes() +
+    return XT.bytes() + norms.bytes() + xlast.bytes() + partial.bytes() + kcache.bytes() + kdesc.bytes() + q.bytes() * 10 + w.bytes() +
            csr_bytes() + lanes.bytes();
 }
 

@@ -20,6 +20,7 @@
 #include <cstdlib>
 
 #include "kernels.hpp"
+#include "kp_pack.hpp"
 
 namespace plssvm_mi {
 
@@ -166,7 +167,8 @@ constexpr bool kp_dma_after_reads() {
 // The multi-vector KP_LOAD keeps the whole record live across the loop over vectors: in fp64 that does not fit 168
 // VGPRs (22 spilled dwords, three of them record chunks whose spill stores wait for their loads right after issue,
 // which serialises the head of the stream), so it runs 2 workgroups per CU with 256 VGPRs; KP_MULTI_LOAD_WAVES=3
-// builds the 3-per-CU variant (A/B in DESIGN.md §3.1.3)
+// builds the 3-per-CU variant (A/B in DESIGN.md §3.1.3). (kp_load_f64 decodes the record once and needs 166 VGPRs:
+// at 3 per CU it no longer spills, and measured faster for 4 and 8 vectors but slower for 1 and 2, §3.1.2.)
 #ifndef KP_MULTI_LOAD_WAVES
 #define KP_MULTI_LOAD_WAVES 2
 #endif
@@ -188,11 +190,185 @@ struct kp_vec<float> {
     typedef float type __attribute__((ext_vector_type(4)));
 };
 
+// The fp64 record loads carry the non-temporal hint: a record is read again only after the rest of the cache (tens
+// of GB) has gone by, so nothing of it is worth keeping in a cache. -DKP_LOAD_NT=0 builds plain loads (A/B in
+// every run with the hint beat every run without)
+#ifndef KP_LOAD_NT
+#define KP_LOAD_NT 1
+#endif
+
+// LDS layout of the epilogue's reduction buffers (element counts): p_I, p_J, n_I, n_J, then row partials
+// [wc][128 rows][16 (+1 pad)] and column partials [wr][128 cols][4 (+1 pad)]
+constexpr int KP_OFF_PAN = 4 * KP_TILE;
+constexpr int KP_RSTR = 17, KP_RHALF = KP_TILE * KP_RSTR + 1, KP_CSTR = 5;
+
+// The fp64 KP_LOAD workgroup: the tile's record -> registers -> the "times p" epilogue of kp_tile_kernel (the same
+// fma chains, LDS park and fixed-order sums, so the slab record is bitwise the computed one). PACKED: the record is
+// the 7-byte form of kp_pack.hpp — 28 dwordx4 per lane instead of 32, each value's high dword rebuilt from its
+// 24-bit word and the tile's base just before its fma. All of the lane's loads are issued before the first use: the
+// whole record (112 or 128 KiB) is in flight. MULTI: the values are decoded once, then multiplied with every live
+// vector as in kp_tile_kernel's MULTI epilogue.
+template <bool PACKED, bool MULTI>
+__device__ __forceinline__ void kp_load_f64(const double *__restrict__ kcache, int64_t wg, uint32_t base,
+                                            const double *__restrict__ p, double *__restrict__ partial, double *smem,
+                                            int tid, int lane, int wr, int wc, bool diag, int64_t pidx, unsigned live,
+                                            int64_t pstride, int64_t sstride) {
+    using M = mfma16<double>;
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef double f64x2 __attribute__((ext_vector_type(2)));
+    // this lane's element of p (MULTI: of the first live vector), ahead of the record: loads return in order, and the
+    // staging barrier below must not wait for the record
+    int c = MULTI ? __builtin_ctz(live) : 0;
+    double pnext = p[MULTI ? c * pstride + pidx : pidx];
+    u32x4 kq[PACKED ? KP_PACK_GROUPS : 1];
+    f64x2 kld[PACKED ? 1 : 32];
+    if constexpr (PACKED) {
+        const u32x4 *rec = reinterpret_cast<const u32x4 *>(kcache + wg * KP_CACHE_REC) + tid;
+#pragma unroll
+        for (int g = 0; g < KP_PACK_GROUPS; ++g) {
+            kq[g] = KP_LOAD_NT ? __builtin_nontemporal_load(rec + g * 256) : rec[g * 256];
+            if constexpr (!MULTI) __builtin_amdgcn_sched_barrier(0);  // issued in record order: they return in order
+        }
+    } else {
+        const f64x2 *rec = reinterpret_cast<const f64x2 *>(kcache + wg * KP_CACHE_REC) + tid;
+#pragma unroll
+        for (int g = 0; g < 32; ++g) {
+            kld[g] = KP_LOAD_NT ? __builtin_nontemporal_load(rec + g * 256) : rec[g * 256];
+            if constexpr (!MULTI) __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    // single vector: nothing of the epilogue moves up between the loads (a use there waits for its load with the rest
+    // unissued), and below one row ends before the next begins, so the waits follow the record's groups as they arrive
+    // (left to itself the scheduler gathers the integer decode of all rows behind the first LDS read: vmcnt(1) at once)
+    if constexpr (!MULTI) __builtin_amdgcn_sched_barrier(0);
+    // value nt of row (mt, r); every index is a constant once the loops are unrolled
+    auto kval = [&](int mt, int r, int nt) -> double {
+        if constexpr (PACKED) {
+            const int d0 = 3 * r;
+            const uint32_t lo = kq[kp_pack_lo_group(mt, r)][nt];
+            const uint32_t hi = kp_unpack4(nt, kq[kp_pack_hi_group(mt, d0)][d0 & 3], kq[kp_pack_hi_group(mt, d0 + 1)][(d0 + 1) & 3],
+                                           kq[kp_pack_hi_group(mt, d0 + 2)][(d0 + 2) & 3], base);
+            return __hiloint2double((int) hi, (int) lo);
+        } else {
+            return kld[((mt * 4 + r) * 4 + nt) / 2][nt & 1];
+        }
+    };
+    const double *pI = smem, *pJ = smem + KP_TILE;
+    double *rowp = smem + KP_OFF_PAN + wc * KP_RHALF;
+    const int q = tid >> 1, h = tid & 1;  // row / column q of the tile, half h
+    if constexpr (!MULTI) {
+        smem[tid] = pnext;
+        __syncthreads();  // p_I, p_J visible
+        double pj[4];
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) pj[nt] = pJ[wc * 64 + nt * 16 + (lane & 15)];
+        double cs[4] = { 0, 0, 0, 0 };
+        double pi = pI[wr * 64 + M::row(lane, 0)];  // one row ahead: its LDS latency lies under the row before
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int il = wr * 64 + mt * 16 + M::row(lane, r);
+                const int rn = mt * 4 + r + 1;  // the next row
+                const double pin = rn < 16 ? pI[wr * 64 + (rn >> 2) * 16 + M::row(lane, rn & 3)] : 0.0;
+                double s = 0;
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) {
+                    const double kv = kval(mt, r, nt);
+                    s = fma(kv, pj[nt], s);
+                    cs[nt] = fma(kv, pi, cs[nt]);
+                }
+                rowp[il * KP_RSTR + (lane & 15)] = s;
+                pi = pin;
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        {  // also on a diagonal tile, whose column sums nobody reads: a store under `if (!diag)` lets the compiler sink
+           // the cs chains into that branch, away from the just-decoded values
+            double *colp = smem + KP_OFF_PAN + 2 * KP_RHALF + wr * KP_TILE * KP_CSTR;
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) colp[(wc * 64 + nt * 16 + (lane & 15)) * KP_CSTR + (lane >> 4)] = cs[nt];
+        }
+        __syncthreads();
+        const double *rp = smem + KP_OFF_PAN + h * KP_RHALF + q * KP_RSTR;
+        double a = rp[0];
+#pragma unroll
+        for (int k = 1; k < 16; ++k) a += rp[k];
+        a += __shfl_xor(a, 1);
+        if (!diag) {
+            const double *cp = smem + KP_OFF_PAN + 2 * KP_RHALF + (h * KP_TILE + q) * KP_CSTR;
+            double c = (cp[0] + cp[1]) + (cp[2] + cp[3]);
+            c += __shfl_xor(c, 1);
+            if (h == 1) partial[wg * KP_REC + KP_TILE + q] = c;  // column sums of the J rows
+        }
+        if (h == 0) partial[wg * KP_REC + q] = a;  // row sums of the I rows
+    } else {
+        double kv[16][4];  // decoded once; the record's registers die here
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) kv[mt * 4 + r][nt] = kval(mt, r, nt);
+        while (true) {  // the next live vector's element is fetched while this one is multiplied
+            smem[tid] = pnext;  // the previous turn's reads of p_I / p_J lie before its second barrier
+            __syncthreads();    // p_c visible; every wave is done with the previous turn's sums
+            const unsigned rest = live >> (c + 1);
+            const int cn = rest != 0 ? c + 1 + __builtin_ctz(rest) : -1;
+            if (cn >= 0) pnext = p[cn * pstride + pidx];
+            double pj[4];
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) pj[nt] = pJ[wc * 64 + nt * 16 + (lane & 15)];
+            double cs[4] = { 0, 0, 0, 0 };
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int il = wr * 64 + mt * 16 + M::row(lane, r);
+                    const double pi = pI[il];
+                    double s = 0;
+#pragma unroll
+                    for (int nt = 0; nt < 4; ++nt) {
+                        s = fma(kv[mt * 4 + r][nt], pj[nt], s);
+                        cs[nt] = fma(kv[mt * 4 + r][nt], pi, cs[nt]);
+                    }
+                    rowp[il * KP_RSTR + (lane & 15)] = s;
+                }
+            }
+            {
+                double *colp = smem + KP_OFF_PAN + 2 * KP_RHALF + wr * KP_TILE * KP_CSTR;
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) colp[(wc * 64 + nt * 16 + (lane & 15)) * KP_CSTR + (lane >> 4)] = cs[nt];
+            }
+            __syncthreads();
+            double *slab = partial + c * sstride;
+            const double *rp = smem + KP_OFF_PAN + h * KP_RHALF + q * KP_RSTR;
+            double a = rp[0];
+#pragma unroll
+            for (int k = 1; k < 16; ++k) a += rp[k];
+            a += __shfl_xor(a, 1);
+            if (!diag) {
+                const double *cp = smem + KP_OFF_PAN + 2 * KP_RHALF + (h * KP_TILE + q) * KP_CSTR;
+                double cc = (cp[0] + cp[1]) + (cp[2] + cp[3]);
+                cc += __shfl_xor(cc, 1);
+                if (h == 1) slab[wg * KP_REC + KP_TILE + q] = cc;  // column sums of the J rows
+            }
+            if (h == 0) slab[wg * KP_REC + q] = a;  // row sums of the I rows
+            if (cn < 0) break;
+            c = cn;
+        }
+    }
+}
+
 // MODE (kernels.hpp): KP_COMPUTE forms the tile's kernel values from the data; KP_COMPUTE_STORE also writes them
 // to the tile's cache record kcache[wg]; KP_LOAD reads them from there and runs the same epilogue from "times p_j"
 // on — the same fma order, LDS park and sums, so the slab record is bitwise the computed one. A cache record is
 // in register layout, [value group][thread][VEC]: a lane's 64 values in (mt, r, nt) order, 16 bytes per lane and
 // group, so every wave-instruction moves one contiguous KiB. wg_base: the first workgroup (tile) of this launch.
+// fp64 records come raw or in the 7-byte form of kp_pack.hpp, per tile (kdesc[wg]: 0 = raw, else the tile's base
+// exponent): the fp64 KP_COMPUTE_STORE instance finds the tile's exponent range, writes the descriptor, counts the
+// packed tiles in *kcount (pack = 0: every tile raw) and stores either form; the fp64 KP_LOAD instance is kp_load_f64
+// above, so the KP_LOAD statements in this body serve fp32 only. fp32 records are always raw.
 //
 // MULTI: nvec (<= KP_MULTI_W) vectors per visit of a tile (the single-vector instances ignore nvec and the
 // strides). Vector c is p + c * pstride, its slab partial + c * sstride, its stop flag status[c]. The tile's kernel
@@ -210,7 +386,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_wav
                                                          const int32_t *__restrict__ wg_off,
                                                          const cg_scalars<T> *__restrict__ status, int64_t wg_base,
                                                          T *__restrict__ kcache, int nvec, int64_t pstride,
-                                                         int64_t sstride) {
+                                                         int64_t sstride, int32_t *__restrict__ kdesc,
+                                                         int32_t *__restrict__ kcount, int pack) {
     static_assert(!MULTI || MODE != KP_COMPUTE_STORE, "the tile cache is filled by the single-vector kernel");
     using M = mfma16<T>;
     using acc_t = typename M::acc_t;
@@ -223,8 +400,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_wav
     // LDS: p_I, p_J, n_I, n_J, then the two double-buffered panel pairs; once the K loop is done the
     // epilogue's reduction buffers overlay the panels: row partials [wc][128 rows][16 (+1 pad)],
     // column partials [wr][128 cols][4 (+1 pad)]
-    constexpr int OFF_PAN = 4 * KP_TILE;
-    constexpr int RSTR = 17, RHALF = KP_TILE * RSTR + 1, CSTR = 5;
+    constexpr int OFF_PAN = KP_OFF_PAN;
+    constexpr int RSTR = KP_RSTR, RHALF = KP_RHALF, CSTR = KP_CSTR;
     constexpr int RED = 2 * RHALF + 2 * KP_TILE * CSTR;
     constexpr int SMEM = OFF_PAN + ((MODE != KP_LOAD && 4 * PANEL > RED) ? 4 * PANEL : RED);
     __shared__ __attribute__((aligned(16))) T smem[SMEM];
@@ -248,6 +425,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_wav
     // range made the last rank of 8 3.9 % slower than the others)
     // (KP_LOAD has no panels to keep in an L2: its workgroups walk the records in order)
     const int64_t wg = wg_base + (MODE == KP_LOAD ? (int64_t) blockIdx.x : xcd_remap(blockIdx.x, gridDim.x));
+    // fp64 records may be in the 7-byte form (kp_pack.hpp): the tile's descriptor, one wave-uniform load issued
+    // ahead of the table search below so that its latency hides there
+    constexpr bool PACK_LOAD = MODE == KP_LOAD && sizeof(T) == 8, PACK_STORE = MODE == KP_COMPUTE_STORE && sizeof(T) == 8;
+    uint32_t desc = KP_PACK_RAW;
+    if constexpr (PACK_LOAD) desc = (uint32_t) kdesc[wg];
     int lo = 0, hi = (int) nsuper;  // largest k with wg_off[k] <= wg
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
@@ -276,6 +458,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_wav
     const int wr = w >> 1, wc = w & 1;
 
     const int64_t pidx = (tid < KP_TILE) ? I0 + tid : J0 + (tid - KP_TILE);
+    if constexpr (PACK_LOAD) {
+        if (desc != KP_PACK_RAW)
+            kp_load_f64<true, MULTI>(kcache, wg, kp_pack_base(desc), p, partial, smem, tid, lane, wr, wc, diag, pidx, live,
+                                     pstride, sstride);
+        else
+            kp_load_f64<false, MULTI>(kcache, wg, 0u, p, partial, smem, tid, lane, wr, wc, diag, pidx, live, pstride,
+                                      sstride);
+        return;
+    }
     acc_t acc[4][4];
     vec_t kld[MODE == KP_LOAD ? NGRP : 1];
     if constexpr (MODE == KP_LOAD) {
@@ -381,10 +572,54 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_wav
         // row-half waves). They are parked in LDS and every thread then sums one half-row and one
         // half-column: ~20 adds per lane instead of a 4-level shuffle tree per row (64 adds + 128
         // ds_bpermute); the fixed summation order keeps K·p bitwise reproducible.
-        __syncthreads();  // every wave is done with the last K chunk: the panels become reduction buffers
+        uint32_t pk_desc = KP_PACK_RAW;  // fp64 KP_COMPUTE_STORE: the tile's descriptor, uniform in the workgroup
+        if constexpr (PACK_STORE) {
+            // The kernel function once, in place (the call and its arguments are those of the loop below, as in the
+            // MULTI branch: the values are bitwise the same), tracking the range of the lane's high dwords; the four
+            // waves' ranges meet in LDS behind the barrier that ends the K loop anyway.
+            __shared__ uint32_t pk_red[8];
+            uint32_t mn = KP_PACK_MN0, mx = KP_PACK_MX0;
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const T ni = nI[wr * 64 + mt * 16 + M::row(lane, r)];
+                    const T ai = FAST_EXP ? -kf.gamma * T(KEXP) * ni : T(0);
+#pragma unroll
+                    for (int nt = 0; nt < 4; ++nt) {
+                        if constexpr (FAST_EXP)
+                            acc[mt][nt][r] = (T) exp_scaled_f64(fma(c2, acc[mt][nt][r], ai), exp_tab);
+                        else
+                            acc[mt][nt][r] = kernel_apply<T>(KERNEL, kf.degree, kf.gamma, kf.coef0, acc[mt][nt][r], ni, nj[nt]);
+                        kp_pack_track((uint32_t) __double2hiint((double) acc[mt][nt][r]), mn, mx);
+                    }
+                }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                mn = min(mn, (uint32_t) __shfl_xor((int) mn, o));
+                mx = max(mx, (uint32_t) __shfl_xor((int) mx, o));
+            }
+            if (lane == 0) {
+                pk_red[2 * w] = mn;
+                pk_red[2 * w + 1] = mx;
+            }
+            __syncthreads();  // every wave is done with the last K chunk: the panels become reduction buffers
+            mn = min(min(pk_red[0], pk_red[2]), min(pk_red[4], pk_red[6]));
+            mx = max(max(pk_red[1], pk_red[3]), max(pk_red[5], pk_red[7]));
+            pk_desc = __builtin_amdgcn_readfirstlane(pack ? kp_pack_desc(mn, mx) : KP_PACK_RAW);
+            if (tid == 0) {
+                kdesc[wg] = (int32_t) pk_desc;
+                if (pk_desc != KP_PACK_RAW) atomicAdd(kcount, 1);  // one per packed tile
+            }
+        } else {
+            __syncthreads();  // every wave is done with the last K chunk: the panels become reduction buffers
+        }
+        const uint32_t pk_base = kp_pack_base(pk_desc);
         T *rowp = smem + OFF_PAN + wc * RHALF;
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
+            uint32_t pk_hw[PACK_STORE ? 12 : 1];  // the mt's 24-bit words: row r in dwords 3r .. 3r + 2
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int il = wr * 64 + mt * 16 + M::row(lane, r);
@@ -398,6 +633,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_wav
                     T kv;
                     if constexpr (MODE == KP_LOAD)
                         kv = kld[((mt * 4 + r) * 4 + nt) / VEC][nt % VEC];
+                    else if constexpr (PACK_STORE)
+                        kv = acc[mt][nt][r];
                     else if constexpr (FAST_EXP)
                         kv = (T) exp_scaled_f64(fma(c2, acc[mt][nt][r], ai), exp_tab);
                     else
@@ -407,7 +644,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_wav
                     cs[nt] = fma(kv, pi, cs[nt]);
                 }
                 rowp[il * RSTR + (lane & 15)] = s;
-                if constexpr (MODE == KP_COMPUTE_STORE) {
+                if constexpr (PACK_STORE) {
+                    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                    if (pk_desc != KP_PACK_RAW) {  // uniform
+                        u32x4 *rec = reinterpret_cast<u32x4 *>(kcache + wg * KP_CACHE_REC) + tid;
+                        uint32_t hi[4];
+                        u32x4 lo;
+#pragma unroll
+                        for (int nt = 0; nt < 4; ++nt) {
+                            lo[nt] = (uint32_t) __double2loint((double) kvs[nt]);
+                            hi[nt] = (uint32_t) __double2hiint((double) kvs[nt]);
+                        }
+                        kp_pack4(hi, pk_base, pk_hw + 3 * r);
+                        rec[kp_pack_lo_group(mt, r) * 256] = lo;
+                        if (r >= 1) {  // dwords 4 (r - 1) .. 4 (r - 1) + 3 are complete
+                            const int d = 4 * (r - 1);
+                            rec[kp_pack_hi_group(mt, d) * 256] = u32x4{ pk_hw[d], pk_hw[d + 1], pk_hw[d + 2], pk_hw[d + 3] };
+                        }
+                    } else {
+                        vec_t *rec = reinterpret_cast<vec_t *>(kcache + wg * KP_CACHE_REC) + tid;
+#pragma unroll
+                        for (int h = 0; h < 4 / VEC; ++h) {
+                            vec_t v;
+#pragma unroll
+                            for (int e = 0; e < VEC; ++e) v[e] = kvs[h * VEC + e];
+                            rec[((mt * 4 + r) * (4 / VEC) + h) * 256] = v;
+                        }
+                    }
+                } else if constexpr (MODE == KP_COMPUTE_STORE) {
                     vec_t *rec = reinterpret_cast<vec_t *>(kcache + wg * KP_CACHE_REC) + tid;
 #pragma unroll
                     for (int h = 0; h < 4 / VEC; ++h) {
@@ -599,12 +863,12 @@ namespace {
 template <typename T, int MODE>
 void launch_kp_mode(kfun<T> kf, const T *XT, const T *norms, const T *p, T *partial, int64_t n_pad, int64_t d_pad,
                     int64_t nb, int64_t s0, int64_t nsuper, const int32_t *wg_off, int64_t base, int64_t count,
-                    const cg_scalars<T> *status, T *kcache, hipStream_t s) {
+                    const cg_scalars<T> *status, T *kcache, int32_t *kdesc, int32_t *kcount, bool pack, hipStream_t s) {
     if (count <= 0) return;
     const dim3 grid((unsigned) count), block(256);
 #define KP_LAUNCH(KERNEL)                                                                                         \
     hipLaunchKernelGGL((kp_tile_kernel<T, KERNEL, MODE>), grid, block, 0, s, kf, XT, norms, p, partial, n_pad, d_pad, \
-                       nb, s0, nsuper, wg_off, status, base, kcache, 1, (int64_t) 0, (int64_t) 0)
+                       nb, s0, nsuper, wg_off, status, base, kcache, 1, (int64_t) 0, (int64_t) 0, kdesc, kcount, pack ? 1 : 0)
     if constexpr (MODE == KP_LOAD) {
         KP_LAUNCH(0);  // one instance per real type: the stored values are past the kernel function
     } else {
@@ -626,21 +890,24 @@ void launch_kp_mode(kfun<T> kf, const T *XT, const T *norms, const T *p, T *part
 template <typename T>
 void launch_kp_tiles(kfun<T> kf, const T *XT, const T *norms, const T *p, T *partial, int64_t n_pad, int64_t d_pad,
                      int64_t nb, int64_t s0, int64_t nsuper, const int32_t *wg_off, int64_t wgs,
-                     const cg_scalars<T> *status, hipStream_t s, T *kcache, int64_t cached, bool fill) {
+                     const cg_scalars<T> *status, hipStream_t s, T *kcache, int64_t cached, bool fill, int32_t *kdesc,
+                     int32_t *kcount, bool pack) {
     if (nsuper <= 0 || nb <= 0 || wgs <= 0) return;
     // 32-bit DMA offsets inside a chunk (kp_tile_kernel): (BK - 1) rows of n_pad plus a tile row
     if ((int64_t) kp_dpad<T>() * n_pad * (int64_t) sizeof(T) >= ((int64_t) 1 << 31))
         throw mi_error(-5, "too many points for the pairwise tile kernel's 32-bit chunk offsets");
     if (kcache == nullptr || cached < 0) cached = 0;
     if (cached > wgs) cached = wgs;
+    if (cached > 0 && sizeof(T) == 8 && (kdesc == nullptr || kcount == nullptr))
+        throw mi_error(-1, "fp64 tile records need their descriptors");
     if (fill)
         launch_kp_mode<T, KP_COMPUTE_STORE>(kf, XT, norms, p, partial, n_pad, d_pad, nb, s0, nsuper, wg_off, 0, cached,
-                                            status, kcache, s);
+                                            status, kcache, kdesc, kcount, pack, s);
     else
         launch_kp_mode<T, KP_LOAD>(kf, XT, norms, p, partial, n_pad, d_pad, nb, s0, nsuper, wg_off, 0, cached, status,
-                                   kcache, s);
+                                   kcache, kdesc, kcount, false, s);
     launch_kp_mode<T, KP_COMPUTE>(kf, XT, norms, p, partial, n_pad, d_pad, nb, s0, nsuper, wg_off, cached, wgs - cached,
-                                  status, nullptr, s);
+                                  status, nullptr, nullptr, nullptr, false, s);
 }
 
 // The batched form: nvec vectors p + c * pstride into the slabs partial + c * sstride, stop flags status[c] (null:
@@ -650,18 +917,19 @@ template <typename T>
 void launch_kp_tiles_multi(kfun<T> kf, const T *XT, const T *norms, const T *p, int64_t pstride, T *partial,
                            int64_t sstride, int nvec, int64_t n_pad, int64_t d_pad, int64_t nb, int64_t s0,
                            int64_t nsuper, const int32_t *wg_off, int64_t wgs, const cg_scalars<T> *status, hipStream_t s,
-                           const T *kcache, int64_t cached) {
+                           const T *kcache, int64_t cached, const int32_t *kdesc) {
     if (nsuper <= 0 || nb <= 0 || wgs <= 0) return;
     if (nvec < 1 || nvec > KP_MULTI_W) throw mi_error(-1, "bad vector count for the batched tile kernel");
     if ((int64_t) kp_dpad<T>() * n_pad * (int64_t) sizeof(T) >= ((int64_t) 1 << 31))
         throw mi_error(-5, "too many points for the pairwise tile kernel's 32-bit chunk offsets");
     if (kcache == nullptr || cached < 0) cached = 0;
     if (cached > wgs) cached = wgs;
+    if (cached > 0 && sizeof(T) == 8 && kdesc == nullptr) throw mi_error(-1, "fp64 tile records need their descriptors");
     const dim3 block(256);
 #define KP_LAUNCH(KERNEL, MODE, base, count)                                                                          \
     hipLaunchKernelGGL((kp_tile_kernel<T, KERNEL, MODE, true>), dim3((unsigned) (count)), block, 0, s, kf, XT, norms, p, \
                        partial, n_pad, d_pad, nb, s0, nsuper, wg_off, status, (int64_t) (base), const_cast<T *>(kcache),  \
-                       nvec, pstride, sstride)
+                       nvec, pstride, sstride, const_cast<int32_t *>(kdesc), (int32_t *) nullptr, 0)
     if (cached > 0) {
         KP_LAUNCH(0, KP_LOAD, 0, cached);
         MI_LAUNCH_CHECK();
@@ -692,10 +960,11 @@ void launch_kp_reduce(const T *partial, int64_t nb, int64_t m, int64_t s0, int64
 #define INST(T)                                                                                                  \
     template void launch_kp_tiles<T>(kfun<T>, const T *, const T *, const T *, T *, int64_t, int64_t, int64_t, \
                                      int64_t, int64_t, const int32_t *, int64_t, const cg_scalars<T> *,        \
-                                     hipStream_t, T *, int64_t, bool);                                          \
+                                     hipStream_t, T *, int64_t, bool, int32_t *, int32_t *, bool);     \
     template void launch_kp_tiles_multi<T>(kfun<T>, const T *, const T *, const T *, int64_t, T *, int64_t, int,  \
                                            int64_t, int64_t, int64_t, int64_t, int64_t, const int32_t *, int64_t,  \
-                                           const cg_scalars<T> *, hipStream_t, const T *, int64_t);               \
+                                           const cg_scalars<T> *, hipStream_t, const T *, int64_t,     \
+                                           const int32_t *);                                                      \
     template void launch_kp_reduce<T>(const T *, int64_t, int64_t, int64_t, int64_t, const int32_t *, T *,     \
                                       const cg_scalars<T> *, hipStream_t);
 INST(float)
