@@ -288,7 +288,8 @@ PLSSVM_MI_API int plssvm_mi_solve_cg_multi(plssvm_mi_ctx *ctx, const void *B, in
  * holding +1 for the points of class c and -1 for all others. Per class exactly plssvm_mi_learn's arithmetic
  * (b = y - y_m, the bias, alpha[m] = -sum): alpha_out[nclass][ldy], bias_out[nclass] (nullable), delta_trace
  * (nullable, [nclass][imax + 1]; with imax < 0: [nclass][num_features + 1]), iters[nclass] (nullable). The class with
- * the largest decision value bias_c + sum_i alpha_ci k(x_i, z) is the prediction (plssvm_mi_predict_* per class). */
+ * the largest decision value bias_c + sum_i alpha_ci k(x_i, z) is the prediction (plssvm_mi_predict_multi_*: every
+ * class's decision values in one call). */
 PLSSVM_MI_API int plssvm_mi_learn_multi(plssvm_mi_ctx *ctx, const void *Y, int64_t nclass, int64_t ldy, int64_t imax,
                                         double eps, void *alpha_out, double *bias_out, double *delta_trace,
                                         int64_t *iters);
@@ -311,6 +312,38 @@ PLSSVM_MI_API int plssvm_mi_predict_dense(plssvm_mi_ctx *ctx, const void *alpha,
 PLSSVM_MI_API int plssvm_mi_predict_csr(plssvm_mi_ctx *ctx, const void *alpha, double bias, const int64_t *rowptr,
                                         const int32_t *col, const void *val, int val_fmt, int64_t np, int64_t d,
                                         void *out);
+
+/* The same for nclass models on the same support vectors (the one-vs-all classes of plssvm_mi_learn_multi), with
+ * the matrix conventions of the _multi block above: ALPHA[nclass][lda] and OUT[nclass][ldo] hold one class per row,
+ * lda >= n, ldo >= np, elements past n (np) of a row are never read (written); bias[nclass]. nclass < 1, a NULL
+ * buffer or a too small leading dimension: PLSSVM_MI_ERR_ARG (the context stays usable); np == 0 is a no-op.
+ * Dense data with the polynomial / rbf kernel runs the fused tile kernel (csrc/predict_tiles.hip): the kernel values
+ * of a (support-vector tile, point tile) pair are formed once on MFMA, never written to memory, and multiplied with
+ * every class's alpha (up to 8 classes per pass over the tiles). Everything else (the linear w path, sparse data)
+ * runs the classes one after another. plssvm_mi_predict_dense / _csr are the nclass = 1 case of these calls.
+ * Contract: the decision value of (class c, point z) depends only on the model (the support vectors, alpha_c,
+ * bias_c, the kernel parameters) and on z. It does not depend on nclass, on the class's position among the
+ * classes, on np, on the point's position in the call, on the chunking of the points, or on the run: row c of OUT is
+ * BITWISE what plssvm_mi_predict_dense / _csr return for (alpha_c, bias_c), for any subset or order of the points.
+ * Environment, read per call: PLSSVM_MI_PRED_GEMM=1 selects the rocBLAS GEMM + epilogue path for dense poly / rbf
+ * (once per class; the A/B baseline), PLSSVM_MI_PRED_CHUNK=<points> overrides the number of points per upload. */
+PLSSVM_MI_API int plssvm_mi_predict_multi_dense(plssvm_mi_ctx *ctx, const void *ALPHA, int64_t nclass, int64_t lda,
+                                                const double *bias, const void *Z, int64_t np, int64_t d, void *OUT,
+                                                int64_t ldo);
+PLSSVM_MI_API int plssvm_mi_predict_multi_csr(plssvm_mi_ctx *ctx, const void *ALPHA, int64_t nclass, int64_t lda,
+                                              const double *bias, const int64_t *rowptr, const int32_t *col,
+                                              const void *val, int val_fmt, int64_t np, int64_t d, void *OUT,
+                                              int64_t ldo);
+
+/* plssvm_mi_info.predict_algo: the path the last predict call of the context took */
+#define PLSSVM_MI_PREDICT_NONE 0      /* no predict call yet */
+#define PLSSVM_MI_PREDICT_LINEAR 1    /* w . z + bias */
+#define PLSSVM_MI_PREDICT_GEMM 2      /* dense poly / rbf: rocBLAS G = X Z^T + epilogue (PLSSVM_MI_PRED_GEMM) */
+#define PLSSVM_MI_PREDICT_TILES 3     /* dense poly / rbf: the fused MFMA tile kernel */
+#define PLSSVM_MI_PREDICT_EXPANSION 4 /* sparse poly / rbf: the kernel expansion */
+#define PLSSVM_MI_PREDICT_BRUTE 5     /* sparse poly / rbf: every support vector entry per 64 points */
+/* support-vector tiles (of tile_rows rows) per workgroup segment of the fused predict kernel */
+#define PLSSVM_MI_PREDICT_SEG_TILES 16
 
 /* Timing hook (bench.py): runs `reps` K·p launches (+ reduction/collective) on resident device
  * buffers (p = a fixed device vector) and reports the average device time per K·p and per
@@ -354,6 +387,7 @@ typedef struct {
     int64_t kp_cache_packed_tiles; /* of kp_cache_tiles: tiles stored at 7 bytes per value (PLSSVM_MI_OPT_KP_PACK);
                                       0 before the first K·p of a setup has filled the cache; read back from the
                                       device on the first request after that */
+    int predict_algo;              /* PLSSVM_MI_PREDICT_*: the path of the context's last predict call */
 } plssvm_mi_info;
 PLSSVM_MI_API int plssvm_mi_get_info(const plssvm_mi_ctx *ctx, plssvm_mi_info *info);
 

@@ -432,12 +432,39 @@ class CSVM:
         self.traces = [trace[c, : it[c] + 1].copy() for c in range(K)]
         return self
 
-    def predict_values_multi(self, points, val_fmt=None):
-        """Decision values [np][K] of the learn_multi model: column k is predict_values with class k's alpha, bias."""
-        if self.alphas is None:
+    def predict_values_multi(self, points, val_fmt=None, alphas=None, biases=None):
+        """Decision values [np][K] of the learn_multi model (or of alphas [K][n], biases [K]) in one call: on dense
+        data with the polynomial / rbf kernel every class shares one pass over the kernel values. Column k is bitwise
+        predict_values with class k's alpha and bias."""
+        alphas = self.alphas if alphas is None else alphas
+        biases = self.biases if biases is None else biases
+        if alphas is None:
             raise ValueError("No alphas provided for prediction!")
-        return np.stack([self.predict_values(points, self.alphas[k], self.biases[k], val_fmt)
-                         for k in range(len(self.classes))], axis=1)
+        A = _rows(alphas, self.dtype, self.num_data_points, "alphas")
+        K, lda = A.shape
+        b = np.zeros(K, dtype=np.float64) if biases is None else np.ascontiguousarray(biases, dtype=np.float64)
+        if b.shape != (K,):
+            raise ValueError(f"biases must have {K} entries")
+        if not self._on_device:
+            self.setup_data_on_device()
+        L = _abi.lib()
+        if isinstance(points, tuple):
+            rowptr, col, val, npts, d = points
+            fmt = _abi.VAL_REAL if val_fmt is None else val_fmt
+            rowptr = np.ascontiguousarray(rowptr, dtype=np.int64)
+            col = np.ascontiguousarray(col, dtype=np.int32)
+            val = np.ascontiguousarray(val, dtype=np.uint32 if fmt == _abi.VAL_FP22 else self.dtype)
+            out = np.zeros((K, max(npts, 1)), dtype=self.dtype)
+            self._check(L.plssvm_mi_predict_multi_csr(self._ctx, _ptr(A), K, lda, _ptr(b), _ptr(rowptr), _ptr(col),
+                                                      _ptr(val), fmt, npts, d, _ptr(out), out.shape[1]))
+            return np.ascontiguousarray(out[:, :npts].T)
+        Z = np.ascontiguousarray(points, dtype=self.dtype)
+        if Z.ndim != 2:
+            raise ValueError("points must be a 2-D array [np][d]")
+        out = np.zeros((K, max(Z.shape[0], 1)), dtype=self.dtype)
+        self._check(L.plssvm_mi_predict_multi_dense(self._ctx, _ptr(A), K, lda, _ptr(b), _ptr(Z), Z.shape[0], Z.shape[1],
+                                                    _ptr(out), out.shape[1]))
+        return np.ascontiguousarray(out[:, : Z.shape[0]].T)
 
     def predict_multi(self, points, val_fmt=None):
         """The class with the largest decision value (the lowest class index on a tie)."""

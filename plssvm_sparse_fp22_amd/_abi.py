@@ -33,6 +33,7 @@ EXPORTS = (
     "plssvm_mi_update_w", "plssvm_mi_predict_dense", "plssvm_mi_predict_csr", "plssvm_mi_setup_coo",
     "plssvm_mi_comm_init_host", "plssvm_mi_kp_part", "plssvm_mi_set_progress", "plssvm_mi_comm_abort",
     "plssvm_mi_kp_multi", "plssvm_mi_solve_cg_multi", "plssvm_mi_learn_multi", "plssvm_mi_time_kp_multi",
+    "plssvm_mi_predict_multi_dense", "plssvm_mi_predict_multi_csr",
 )
 OPT_SIM_RANK = 2
 OPT_RBF_FORM = 3
@@ -44,6 +45,9 @@ OPT_KP_PACK = 8
 SPARSE_AUTO, SPARSE_PATTERN, SPARSE_EXPANSION, SPARSE_DENSE, SPARSE_ONTHEFLY = 0, 1, 2, 3, 4
 PART_KERNEL, PART_OVERLAP, PART_REMAINDER = 0, 1, 2
 XCHG_ALLREDUCE, XCHG_ALLGATHER = 0, 1
+# Info.predict_algo: the path of the last predict call (PLSSVM_MI_PREDICT_*)
+PREDICT_NONE, PREDICT_LINEAR, PREDICT_GEMM, PREDICT_TILES, PREDICT_EXPANSION, PREDICT_BRUTE = 0, 1, 2, 3, 4, 5
+PREDICT_SEG_TILES = 16  # support-vector tiles per workgroup segment of the fused predict kernel
 # int fn(void *buf, int64_t count, int real_bytes, int op, void *user)   (plssvm_mi_exchange_fn)
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
                                ctypes.c_void_p)
@@ -61,7 +65,8 @@ class Info(ctypes.Structure):
                 ("exp_waves", ctypes.c_int), ("exp_chunks", ctypes.c_int64), ("exp_hbytes", ctypes.c_int),
                 ("exp_layout", ctypes.c_int), ("exp_dot2", ctypes.c_int), ("centered", ctypes.c_int),
                 ("exp_lt", ctypes.c_int), ("kp_cache_tiles", ctypes.c_int64), ("kp_cache_bytes", ctypes.c_int64),
-                ("multi_width", ctypes.c_int), ("kp_cache_packed_tiles", ctypes.c_int64)]
+                ("multi_width", ctypes.c_int), ("kp_cache_packed_tiles", ctypes.c_int64),
+                ("predict_algo", ctypes.c_int)]
 
 
 class BackendError(RuntimeError):
@@ -125,6 +130,8 @@ def _declare(L):
         "plssvm_mi_solve_cg_multi": ([P, P, I64, I64, P, I64, D, P, P, P], I),
         "plssvm_mi_learn_multi": ([P, P, I64, I64, I64, D, P, P, P, P], I),
         "plssvm_mi_time_kp_multi": ([P, I64, I, PD], I),
+        "plssvm_mi_predict_multi_dense": ([P, P, I64, I64, P, P, I64, I64, P, I64], I),
+        "plssvm_mi_predict_multi_csr": ([P, P, I64, I64, P, P, P, P, I, I64, I64, P, I64], I),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

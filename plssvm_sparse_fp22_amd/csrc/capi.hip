@@ -3,6 +3,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "../../include/plssvm_mi355x.h"
 #include "engine.hpp"
@@ -405,6 +406,34 @@ int plssvm_mi_predict_csr(plssvm_mi_ctx *ctx, const void *alpha, double bias, co
     });
 }
 
+static_assert(PLSSVM_MI_PREDICT_SEG_TILES == plssvm_mi::PRED_SEG, "the header states the segment length");
+
+int plssvm_mi_predict_multi_dense(plssvm_mi_ctx *ctx, const void *ALPHA, int64_t nclass, int64_t lda, const double *bias,
+                                  const void *Z, int64_t np, int64_t d, void *OUT, int64_t ldo) {
+    if (!ctx || nclass < 1 || !ALPHA || !bias) return PLSSVM_MI_ERR_ARG;
+    return ctx->call([&](auto &e) {
+        using T = std::remove_reference_t<decltype(e.gamma)>;
+        if (np > 0 && (Z == nullptr || OUT == nullptr)) throw plssvm_mi::mi_error(PLSSVM_MI_ERR_ARG, "no points to predict");
+        std::vector<T> b(bias, bias + nclass);
+        e.predict_multi(static_cast<const T *>(ALPHA), nclass, lda, b.data(), static_cast<const T *>(Z), nullptr, nullptr,
+                        nullptr, PLSSVM_MI_VAL_REAL, np, d, static_cast<T *>(OUT), ldo);
+    });
+}
+
+int plssvm_mi_predict_multi_csr(plssvm_mi_ctx *ctx, const void *ALPHA, int64_t nclass, int64_t lda, const double *bias,
+                                const int64_t *rowptr, const int32_t *col, const void *val, int val_fmt, int64_t np,
+                                int64_t d, void *OUT, int64_t ldo) {
+    if (!ctx || nclass < 1 || !ALPHA || !bias) return PLSSVM_MI_ERR_ARG;
+    return ctx->call([&](auto &e) {
+        using T = std::remove_reference_t<decltype(e.gamma)>;
+        if (np > 0 && (rowptr == nullptr || col == nullptr || (val == nullptr && rowptr[np] > 0) || OUT == nullptr))
+            throw plssvm_mi::mi_error(PLSSVM_MI_ERR_ARG, "no points to predict");
+        std::vector<T> b(bias, bias + nclass);
+        e.predict_multi(static_cast<const T *>(ALPHA), nclass, lda, b.data(), nullptr, rowptr, col, val, val_fmt, np, d,
+                        static_cast<T *>(OUT), ldo);
+    });
+}
+
 int plssvm_mi_get_info(const plssvm_mi_ctx *cctx, plssvm_mi_info *info) {
     if (!cctx || !info) return PLSSVM_MI_ERR_ARG;
     auto *ctx = const_cast<plssvm_mi_ctx *>(cctx);
@@ -449,6 +478,7 @@ int plssvm_mi_get_info(const plssvm_mi_ctx *cctx, plssvm_mi_info *info) {
         info->kp_cache_bytes = e.kcache.bytes();
         info->multi_width = e.multi_width_next();
         info->kp_cache_packed_tiles = e.kcache_packed();
+        info->predict_algo = e.predict_algo;
     });
 }
 

@@ -316,7 +316,17 @@ struct engine : engine_base {
     void update_w_device(const T *alpha_dev);  // w = sum_i alpha_i x_i (device alpha[n])
     void update_w(const T *alpha_host, T *w_host);
     void predict(const T *alpha_host, T bias, const T *Z, const int64_t *zrowptr, const int32_t *zcol, const void *zval,
-                 int zfmt, int64_t np, int64_t dz, T *out);
+                 int zfmt, int64_t np, int64_t dz, T *out);  // predict_multi with nclass = 1
+    // nclass models on the context's support vectors: alpha[nclass][lda], bias[nclass], out[nclass][ldo] (host). Dense
+    // data with the polynomial / rbf kernel: predict_tiles, every class in one pass over the kernel values; everything
+    // else: the classes one after another through predict_one. Row c is bitwise the single call with (alpha_c, bias_c)
+    void predict_multi(const T *alpha_host, int64_t nclass, int64_t lda, const T *bias, const T *Z, const int64_t *zrowptr,
+                       const int32_t *zcol, const void *zval, int zfmt, int64_t np, int64_t dz, T *out, int64_t ldo);
+    void predict_tiles(const T *alpha_host, int64_t nclass, int64_t lda, const T *bias, const T *Z, const int64_t *zrowptr,
+                       const int32_t *zcol, const void *zval, int zfmt, int64_t np, T *out, int64_t ldo);
+    void predict_one(const T *alpha_host, T bias, const T *Z, const int64_t *zrowptr, const int32_t *zcol, const void *zval,
+                     int zfmt, int64_t np, T *out);
+    int predict_algo = 0;  // PLSSVM_MI_PREDICT_*: the path of the last predict call
 
     void allreduce(T *buf, int64_t count);
     // setup decisions of a real group: every rank's K values, rank-major (world == 1: the local ones)

@@ -90,6 +90,29 @@ void launch_kp_tiles_multi(kfun<T> kf, const T *XT, const T *norms, const T *p, 
                            int64_t nsuper, const int32_t *wg_off, int64_t wgs, const cg_scalars<T> *status, hipStream_t s,
                            const T *kcache = nullptr, int64_t cached = 0, const int32_t *kdesc = nullptr);
 
+// ---- fused dense predict tiles (predict_tiles.hip) -------------------------------------------------
+// One workgroup owns a 128-point tile and one segment of PRED_SEG consecutive 128-row support-vector tiles. The
+// segment length is a compile-time constant: it fixes the summation order of a decision value, which therefore
+// depends only on the model and the point (not on the number of points or classes, the chunking or the run).
+constexpr int PRED_SEG = 16;
+inline int64_t predict_segments(int64_t nb) { return (nb + PRED_SEG - 1) / PRED_SEG; }
+// part[c][segment][p] = sum over the segment's support vectors j (tile after tile) of A[c][j] k(x_j, z_p) for the
+// ncls <= KP_MULTI_W classes A[ncls][n_pad] (zero from row m on) and the points ZT[d_pad][np_pad] (feature-major,
+// zero padded; znorms: their squared norms, rbf only). part is [ncls][predict_segments(nb)][np_pad]; polynomial
+// and rbf kernels only; the point tiles covering points [0, npoints) are computed. The kernel values are formed once
+// per tile on MFMA and never leave the registers.
+template <typename T>
+void launch_predict_tiles(kfun<T> kf, const T *XT, const T *norms, int64_t n_pad, int64_t nb, int64_t d_pad,
+                          const T *ZT, const T *znorms, int64_t np_pad, int64_t npoints, const T *A, int ncls, T *part,
+                          hipStream_t s);
+// out[c][p] = ((sum_s part[c][s][p], in segment order) + ab[c] k(xlast, z_p)) + ab[nclass + c] for c < ncls, p < np;
+// out is [ncls][np_pad]. ab = the classes' alpha[m], then their biases (nclass each; the caller offsets it to the
+// first class of part)
+template <typename T>
+void launch_predict_finish(kfun<T> kf, const T *part, int64_t nseg, const T *ZT, const T *znorms, int64_t np_pad,
+                           int64_t d, const T *xlast, T nlast, const T *ab, int ncls, int nclass, int64_t np, T *out,
+                           hipStream_t s);
+
 // raw[i] = sum over the column blocks c in order of row i's slab values of the tiles whose super-block lies
 // in [s0, s1) (tile (Ib, c) row sums for c <= Ib, tile (c, Ib) column sums for c > Ib); i < m
 template <typename T>

@@ -9,9 +9,12 @@
 // taken); this follows the OpenMP semantics (src/plssvm/backends/OpenMP/csvm.cpp:193-240).
 //
 // Layouts:
-//   * dense data: G = X_m Z^T for a chunk of points on rocBLAS (a plain GEMM: library territory),
-//     then one workgroup per point applies the kernel function and reduces sum_i alpha_i k_ip in a
-//     fixed order (no atomics: a prediction is bitwise reproducible);
+//   * dense data, poly / rbf: the fused MFMA tile kernel of predict_tiles.hip — the kernel values of a
+//     (support-vector tile, point tile) pair are formed once, never written to HBM, and multiplied with every
+//     class's alpha while they are in registers (predict_tiles below);
+//   * PLSSVM_MI_PRED_GEMM=1 (read per call; the A/B baseline and fallback): G = X_m Z^T for a chunk of points
+//     on rocBLAS, then one workgroup per point applies the kernel function and reduces sum_i alpha_i k_ip in a
+//     fixed order, once per class (no atomics either way: a prediction is bitwise reproducible);
 //   * sparse data: one wave per CSR row and one lane per predict point (64 points per launch); the
 //     chunk's points are densified feature-major (ZT[f][64]) so the per-entry gather is one
 //     coalesced 64-lane read, partial sums per row block, reduced in block order.
@@ -255,21 +258,12 @@ void engine<T>::update_w(const T *alpha_host, T *w_host) {
     MI_HIP_CHECK(hipStreamSynchronize(stream));
 }
 
-// gpu_csvm::predict (src/plssvm/backends/gpu_csvm.cpp:52-120). Points: dense row-major Z[np][dz] or
-// CSR (zrowptr, zcol, zval in zfmt); out[np] host.
+// One class through the paths that do not batch classes: linear (w . z), dense poly / rbf on rocBLAS + epilogue
+// (PLSSVM_MI_PRED_GEMM), sparse data through the kernel expansion or the brute-force kernel. Arguments are
+// validated by predict_multi. Sets predict_algo.
 template <typename T>
-void engine<T>::predict(const T *alpha_host, T bias, const T *Z, const int64_t *zrowptr, const int32_t *zcol,
-                        const void *zval, int zfmt, int64_t np, int64_t dz, T *out) {
-    need_data();
-    if (np == 0) return;  // "return empty vector if there are no points to predict"
-    if (np < 0 || (Z == nullptr && (zrowptr == nullptr || zcol == nullptr))) throw mi_error(-1, "no points to predict");
-    if (dz != d)
-        throw mi_error(-1, "Number of features per data point (" + std::to_string(d) +
-                               ") must match the number of features per predict point (" + std::to_string(dz) + ")!");
-    if (alpha_host == nullptr) throw mi_error(-1, "No alphas provided for prediction!");
-    if (out == nullptr) throw mi_error(-1, "no output buffer");
-    if (Z == nullptr && zfmt != PLSSVM_MI_VAL_REAL && zfmt != PLSSVM_MI_VAL_FP22) throw mi_error(-1, "unknown value format");
-    if (Z == nullptr && zfmt == PLSSVM_MI_VAL_FP22 && sizeof(T) != 4) throw mi_error(-5, "FP22 values need a float context");
+void engine<T>::predict_one(const T *alpha_host, T bias, const T *Z, const int64_t *zrowptr, const int32_t *zcol,
+                            const void *zval, int zfmt, int64_t np, T *out) {
     MI_HIP_CHECK(hipSetDevice(device));
     dev_buf<T> a;
     a.alloc(std::max<int64_t>(n_pad, n), stream);
@@ -291,6 +285,7 @@ void engine<T>::predict(const T *alpha_host, T bias, const T *Z, const int64_t *
     for (int64_t k = 0; k < d; ++k) nlast = std::fma(xlast_h[k], xlast_h[k], nlast);
 
     if (kernel == 0) {  // w . z + bias
+        predict_algo = PLSSVM_MI_PREDICT_LINEAR;
         update_w_device(a.get());
         const int64_t pc = std::max<int64_t>(1, std::min<int64_t>(np, (int64_t) (256 << 20) / (int64_t) (sizeof(T) * std::max<int64_t>(d, 1))));
         std::vector<T> zh((size_t) (pc * d));
@@ -313,6 +308,7 @@ void engine<T>::predict(const T *alpha_host, T bias, const T *Z, const int64_t *
     if (!sparse) {
         // G = X_m Z^T on rocBLAS (column-major views: XT is (n_pad x d) with ld n_pad, a row-major
         // chunk of points is (d x c) with ld d), then the kernel-function / alpha epilogue
+        predict_algo = PLSSVM_MI_PREDICT_GEMM;
         if (blas == nullptr) MI_BLAS_CHECK(rocblas_create_handle(&blas));
         MI_BLAS_CHECK(rocblas_set_stream(blas, stream));
         const int64_t ldg = std::max<int64_t>(m, 1);
@@ -398,11 +394,13 @@ void engine<T>::predict(const T *alpha_host, T bias, const T *Z, const int64_t *
         oall.alloc(np, stream, false);
         if (expansion_predict(a.get(), alpha_host[m], bias, zrd.get(), zcd.get(), zvd.get(), np, max_nnz_z, zabs_max,
                               znorm_max, nlast, oall.get())) {
+            predict_algo = PLSSVM_MI_PREDICT_EXPANSION;
             MI_HIP_CHECK(hipMemcpyAsync(out, oall.get(), sizeof(T) * (size_t) np, hipMemcpyDeviceToHost, stream));
             MI_HIP_CHECK(hipStreamSynchronize(stream));
             return;
         }
     }
+    predict_algo = PLSSVM_MI_PREDICT_BRUTE;
     const int64_t nblk = std::max<int64_t>(1, ceil_div(m, PRED_ROWS));
     dev_buf<T> ztd, nzd, pd, od;
     ztd.alloc(d * 64, stream, false);
@@ -429,11 +427,128 @@ void engine<T>::predict(const T *alpha_host, T bias, const T *Z, const int64_t *
     }
 }
 
+// Dense data, poly / rbf: all classes per pass over the kernel values (predict_tiles.hip). The points go up in chunks,
+// straight from the caller's row-major buffer (CSR points: densified per chunk on the host), are transposed to
+// ZT[d_pad][chunk] on the device, and each chunk's decision values come back per class row.
+template <typename T>
+void engine<T>::predict_tiles(const T *alpha_host, int64_t nclass, int64_t lda, const T *bias, const T *Z,
+                              const int64_t *zrowptr, const int32_t *zcol, const void *zval, int zfmt, int64_t np, T *out,
+                              int64_t ldo) {
+    MI_HIP_CHECK(hipSetDevice(device));
+    predict_algo = PLSSVM_MI_PREDICT_TILES;
+    const int ncp = (int) std::min<int64_t>(nclass, KP_MULTI_W);  // classes per pass
+    const int64_t nseg = predict_segments(nb);
+    // the model: A[nclass][n_pad], zero from row m on; the classes' alpha[m], then their biases
+    dev_buf<T> A, ab;
+    A.alloc(nclass * n_pad, stream);
+    std::vector<T> abh((size_t) (2 * nclass));
+    for (int64_t c = 0; c < nclass; ++c) {
+        if (m > 0)
+            MI_HIP_CHECK(hipMemcpyAsync(A.get() + c * n_pad, alpha_host + c * lda, sizeof(T) * (size_t) m, hipMemcpyHostToDevice, stream));
+        abh[(size_t) c] = alpha_host[c * lda + m];
+        abh[(size_t) (nclass + c)] = bias[c];
+    }
+    ab.alloc(2 * nclass, stream, false);
+    MI_HIP_CHECK(hipMemcpyAsync(ab.get(), abh.data(), sizeof(T) * (size_t) (2 * nclass), hipMemcpyHostToDevice, stream));
+    T nlast = 0;
+    for (int64_t k = 0; k < d; ++k) nlast = std::fma(xlast_h[k], xlast_h[k], nlast);
+
+    // chunk of points: 512 MiB over the uploaded rows, ZT, the norms, part and out; PLSSVM_MI_PRED_CHUNK=<points>
+    // overrides it (read per call). The tile kernel's 32-bit chunk offsets bound the padded chunk.
+    const int64_t budget = (int64_t) 512 << 20;
+    const int64_t per_point = (int64_t) sizeof(T) * (d_pad + d + 1 + (int64_t) ncp * nseg + nclass);
+    const int64_t pc_max = (((int64_t) 1 << 31) / ((int64_t) kp_dpad<T>() * (int64_t) sizeof(T)) - 1) / KP_TILE * KP_TILE;
+    int64_t pc = std::min(pc_max, std::max<int64_t>(KP_TILE, budget / per_point / KP_TILE * KP_TILE));
+    pc = round_up(ceil_div(np, ceil_div(np, pc)), KP_TILE);  // equal chunks: no short last launch
+    if (const char *e = std::getenv("PLSSVM_MI_PRED_CHUNK")) {
+        const long long v = std::atoll(e);
+        if (v > 0) pc = std::min<int64_t>((int64_t) v, pc_max);
+    }
+    pc = std::min(pc, np);
+    const int64_t pcp = round_up(pc, KP_TILE);
+    dev_buf<T> zd, ztd, nzd, pd, od;
+    zd.alloc(pc * d, stream, false);
+    ztd.alloc(d_pad * pcp, stream);
+    nzd.alloc(pcp, stream);
+    pd.alloc(std::max<int64_t>((int64_t) ncp * nseg * pcp, 1), stream, false);
+    od.alloc(nclass * pcp, stream, false);
+    std::vector<T> zh;
+    if (Z == nullptr) zh.resize((size_t) (pc * d));
+    for (int64_t p0 = 0; p0 < np; p0 += pc) {
+        const int64_t c = std::min(pc, np - p0);
+        const T *src = Z != nullptr ? Z + p0 * d : zh.data();
+        if (Z == nullptr) {
+            std::fill(zh.begin(), zh.begin() + (size_t) (c * d), T(0));
+            for (int64_t p = 0; p < c; ++p)
+                for (int64_t e = zrowptr[p0 + p]; e < zrowptr[p0 + p + 1]; ++e) {
+                    if (zcol[e] < 0 || zcol[e] >= d) throw mi_error(-1, "CSR column index out of range");
+                    zh[(size_t) (p * d + zcol[e])] = zfmt == PLSSVM_MI_VAL_FP22 ? (T) fp22_get(static_cast<const uint32_t *>(zval), e)
+                                                                                : static_cast<const T *>(zval)[e];
+                }
+        }
+        MI_HIP_CHECK(hipMemcpyAsync(zd.get(), src, sizeof(T) * (size_t) (c * d), hipMemcpyHostToDevice, stream));
+        // columns >= c keep an earlier chunk's points: computed, never stored, and no point's value depends on another's
+        launch_transpose<T>(zd.get(), c, d, ztd.get(), pcp, stream);
+        if (kernel == 2) launch_row_norms<T>(ztd.get(), pcp, d, nzd.get(), stream);
+        for (int64_t c0 = 0; c0 < nclass; c0 += ncp) {
+            const int nc = (int) std::min<int64_t>(ncp, nclass - c0);
+            launch_predict_tiles<T>(kf(), XT.get(), norms.get(), n_pad, nb, d_pad, ztd.get(), nzd.get(), pcp, c,
+                                    A.get() + c0 * n_pad, nc, pd.get(), stream);
+            launch_predict_finish<T>(kf(), pd.get(), nseg, ztd.get(), nzd.get(), pcp, d, xlast.get(), nlast, ab.get() + c0,
+                                     nc, (int) nclass, c, od.get() + c0 * pcp, stream);
+        }
+        for (int64_t k = 0; k < nclass; ++k)
+            MI_HIP_CHECK(hipMemcpyAsync(out + k * ldo + p0, od.get() + k * pcp, sizeof(T) * (size_t) c, hipMemcpyDeviceToHost, stream));
+        MI_HIP_CHECK(hipStreamSynchronize(stream));
+    }
+}
+
+// gpu_csvm::predict (src/plssvm/backends/gpu_csvm.cpp:52-120) for nclass models on the same support vectors:
+// alpha_host[nclass][lda] and bias[nclass] (host), out[nclass][ldo] (host). Points: dense row-major Z[np][dz] or CSR
+// (zrowptr, zcol, zval in zfmt). Dense data with the polynomial / rbf kernel: the fused tile kernel, all classes per
+// pass (PLSSVM_MI_PRED_GEMM=1, read per call: rocBLAS + epilogue, once per class). Everything else — the linear w
+// path, sparse data — runs the classes one after another through predict_one. Row c is bitwise the nclass = 1 call
+// with (alpha_c, bias_c).
+template <typename T>
+void engine<T>::predict_multi(const T *alpha_host, int64_t nclass, int64_t lda, const T *bias, const T *Z,
+                              const int64_t *zrowptr, const int32_t *zcol, const void *zval, int zfmt, int64_t np,
+                              int64_t dz, T *out, int64_t ldo) {
+    need_data();
+    if (nclass < 1) throw mi_error(-1, "nclass must be at least 1");
+    if (np == 0) return;  // "return empty vector if there are no points to predict"
+    if (np < 0 || (Z == nullptr && (zrowptr == nullptr || zcol == nullptr))) throw mi_error(-1, "no points to predict");
+    if (dz != d)
+        throw mi_error(-1, "Number of features per data point (" + std::to_string(d) +
+                               ") must match the number of features per predict point (" + std::to_string(dz) + ")!");
+    if (alpha_host == nullptr) throw mi_error(-1, "No alphas provided for prediction!");
+    if (out == nullptr) throw mi_error(-1, "no output buffer");
+    if (Z == nullptr && zfmt != PLSSVM_MI_VAL_REAL && zfmt != PLSSVM_MI_VAL_FP22) throw mi_error(-1, "unknown value format");
+    if (Z == nullptr && zfmt == PLSSVM_MI_VAL_FP22 && sizeof(T) != 4) throw mi_error(-5, "FP22 values need a float context");
+    if (bias == nullptr) throw mi_error(-1, "no biases");
+    if (lda < n || ldo < np) throw mi_error(-1, "leading dimension too small");
+    const char *ge = std::getenv("PLSSVM_MI_PRED_GEMM");
+    const bool gemm = ge != nullptr && std::strcmp(ge, "0") != 0;
+    if (!sparse && kernel != 0 && !gemm) {
+        predict_tiles(alpha_host, nclass, lda, bias, Z, zrowptr, zcol, zval, zfmt, np, out, ldo);
+        return;
+    }
+    for (int64_t c = 0; c < nclass; ++c)
+        predict_one(alpha_host + c * lda, bias[c], Z, zrowptr, zcol, zval, zfmt, np, out + c * ldo);
+}
+
+template <typename T>
+void engine<T>::predict(const T *alpha_host, T bias, const T *Z, const int64_t *zrowptr, const int32_t *zcol,
+                        const void *zval, int zfmt, int64_t np, int64_t dz, T *out) {
+    predict_multi(alpha_host, 1, n, &bias, Z, zrowptr, zcol, zval, zfmt, np, dz, out, std::max<int64_t>(np, 1));
+}
+
 #define INST(T)                                                                                                   \
     template void engine<T>::update_w_device(const T *);                                                        \
     template void engine<T>::update_w(const T *, T *);                                                          \
     template void engine<T>::predict(const T *, T, const T *, const int64_t *, const int32_t *, const void *, int, \
-                                     int64_t, int64_t, T *);
+                                     int64_t, int64_t, T *);                                                    \
+    template void engine<T>::predict_multi(const T *, int64_t, int64_t, const T *, const T *, const int64_t *,  \
+                                           const int32_t *, const void *, int, int64_t, int64_t, T *, int64_t);
 INST(float)
 INST(double)
 #undef INST

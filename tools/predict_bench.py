@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """predict / update_w throughput on BASELINE-shaped models (SURVEY §8(f)2 measurement; run on the GPU box).
 
-* dense RBF, config 2's model: 100k support vectors x 256 fp64, 100k predict points: the GEMM
-  G = X Z^T (2 d n np FLOP) on rocBLAS + the kernel/alpha epilogue; reported against the fp64 MFMA peak;
+* dense RBF, config 2's model: 100k support vectors x 256 fp64, 100k predict points: the fused MFMA tile
+  kernel (csrc/predict_tiles.hip), 2 d n np FLOP whatever the number of classes; reported against the fp64
+  MFMA peak. --classes K[,K...] runs only this row, once per K, through predict_values_multi (K one-vs-all
+  classes in one call); --gemm sets PLSSVM_MI_PRED_GEMM=1 (rocBLAS G = X Z^T + the kernel/alpha epilogue,
+  once per class: the A/B baseline). The kernel's share of the seconds comes from a kernel trace of this
+  command (rocprofv3 --kernel-trace --stats -- python tools/predict_bench.py --classes 8; tools/top_kernels.py);
 * sparse RBF, config 3-RBF's model: 1M support vectors x 50k CSR fp32 (5e7 entries), 4096 CSR points:
   through the kernel expansion (the model's column moments once, then per point its features' moment
   sums and the support vectors sharing two or more features with it), beside the brute-force kernel
@@ -11,6 +15,7 @@
 Times include the host transfers of the points and results (the C ABI takes host buffers); alpha is
 random (the model's alphas do not change the work). Prints one JSON line.
 """
+import argparse
 import json
 import os
 import sys
@@ -32,23 +37,50 @@ def timed(fn, reps=3):
     return (time.perf_counter() - t0) / reps, out
 
 
+ALGO = {v: k for k, v in vars(pm._abi).items() if k.startswith("PREDICT_") and k != "PREDICT_SEG_TILES"}
+
+
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--classes", default=None, metavar="K[,K...]",
+                    help="only the dense row, with K one-vs-all classes per predict_values_multi call")
+    ap.add_argument("--gemm", action="store_true", help="PLSSVM_MI_PRED_GEMM=1: rocBLAS + epilogue, once per class")
+    ap.add_argument("--points", type=int, default=100_000, help="support vectors and predict points of the dense row")
+    ap.add_argument("--reps", type=int, default=3)
+    args = ap.parse_args()
+    if args.gemm:
+        os.environ["PLSSVM_MI_PRED_GEMM"] = "1"
     res = {}
     rng = np.random.default_rng(7)
     # dense RBF (config 2 model)
-    n, d, npts = 100_000, 256, 100_000
+    n, d, npts = args.points, 256, args.points
     X, y = datagen.blobs(n, d, seed=2)
     Z, _ = datagen.blobs(npts, d, seed=9)
     p = pm.Parameter("rbf", gamma=1.0 / d, real_type=np.float64)
     p.data, p.labels = X, y
+    flop = 2.0 * d * n * npts
     with pm.CSVM(p) as svm:
         svm.setup_data_on_device()
         alpha = rng.standard_normal(n)
-        s, _ = timed(lambda: svm.predict_values(Z, alpha=alpha, bias=0.1))
-    flop = 2.0 * d * n * npts
-    res["dense_rbf_100k"] = {"support_vectors": n, "d": d, "points": npts, "dtype": "f64", "seconds": s,
-                             "points_per_s": npts / s, "gemm_TFLOPs": flop / s / 1e12,
-                             "frac_of_fp64_mfma_peak": flop / s / 78.6e12}
+        if args.classes is None:
+            s, _ = timed(lambda: svm.predict_values(Z, alpha=alpha, bias=0.1), args.reps)
+            res["dense_rbf_100k"] = {"support_vectors": n, "d": d, "points": npts, "dtype": "f64", "seconds": s,
+                                     "points_per_s": npts / s, "TFLOPs_on_2dnnp": flop / s / 1e12,
+                                     "frac_of_fp64_mfma_peak": flop / s / 78.6e12,
+                                     "predict_algo": ALGO[svm.info()["predict_algo"]]}
+        else:
+            row = {"support_vectors": n, "d": d, "points": npts, "dtype": "f64", "reps": args.reps}
+            for k in (int(v) for v in args.classes.split(",")):
+                A = rng.standard_normal((k, n))
+                b = rng.standard_normal(k)
+                s, _ = timed(lambda: svm.predict_values_multi(Z, alphas=A, biases=b), args.reps)
+                row[f"K{k}"] = {"seconds": s, "seconds_per_class": s / k, "TFLOPs_on_2dnnp": flop / s / 1e12,
+                                "frac_of_fp64_mfma_peak": flop / s / 78.6e12,
+                                "predict_algo": ALGO[svm.info()["predict_algo"]]}
+            res["dense_rbf_100k"] = row
+    if args.classes is not None:
+        print(json.dumps(res), flush=True)
+        return
     # sparse RBF (config 3-RBF model) and linear update_w (config 3)
     n, d, k, npts = 1_000_000, 50_000, 50, 4096
     csr, y = datagen.sparse_csr(n, d, k, seed=3, dtype=np.float32)
