@@ -388,6 +388,9 @@ typedef struct {
                                       0 before the first K·p of a setup has filled the cache; read back from the
                                       device on the first request after that */
     int predict_algo;              /* PLSSVM_MI_PREDICT_*: the path of the context's last predict call */
+    int rbf_shift;                 /* 1: dense RBF data, the device holds x - c (c = the training data's column means,
+                                      rounded to the real type) and shifts every predict point alike; k(x, z) and every
+                                      result are those of the caller's features. Read-only */
 } plssvm_mi_info;
 PLSSVM_MI_API int plssvm_mi_get_info(const plssvm_mi_ctx *ctx, plssvm_mi_info *info);
 

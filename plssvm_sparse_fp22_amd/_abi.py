@@ -66,7 +66,7 @@ class Info(ctypes.Structure):
                 ("exp_layout", ctypes.c_int), ("exp_dot2", ctypes.c_int), ("centered", ctypes.c_int),
                 ("exp_lt", ctypes.c_int), ("kp_cache_tiles", ctypes.c_int64), ("kp_cache_bytes", ctypes.c_int64),
                 ("multi_width", ctypes.c_int), ("kp_cache_packed_tiles", ctypes.c_int64),
-                ("predict_algo", ctypes.c_int)]
+                ("predict_algo", ctypes.c_int), ("rbf_shift", ctypes.c_int)]
 
 
 class BackendError(RuntimeError):

@@ -479,6 +479,7 @@ int plssvm_mi_get_info(const plssvm_mi_ctx *cctx, plssvm_mi_info *info) {
         info->multi_width = e.multi_width_next();
         info->kp_cache_packed_tiles = e.kcache_packed();
         info->predict_algo = e.predict_algo;
+        info->rbf_shift = (!e.sparse && e.shifted) ? 1 : 0;
     });
 }
 

@@ -51,6 +51,16 @@ __global__ __launch_bounds__(256) void transpose_kernel(const T *__restrict__ X,
     }
 }
 
+// The RBF kernel does not change when every point moves by the same vector: x - c in T, c = the training data's
+// column means, keeps |a|^2 + |b|^2 - 2 a.b from cancelling on features far from the origin.
+template <typename T>
+__global__ __launch_bounds__(256) void shift_rows_kernel(T *__restrict__ X, int64_t total, int64_t d,
+                                                         const T *__restrict__ c) {
+    const int64_t e = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    X[e] = X[e] - c[e % d];
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void row_norms_kernel(const T *__restrict__ XT, int64_t n_pad, int64_t d,
                                                         T *__restrict__ norms) {
@@ -156,6 +166,13 @@ void launch_transpose(const T *X, int64_t rows, int64_t d, T *XT, int64_t n_pad,
 }
 
 template <typename T>
+void launch_shift_rows(T *X, int64_t rows, int64_t d, const T *c, hipStream_t s) {
+    if (rows <= 0 || d <= 0) return;
+    hipLaunchKernelGGL(shift_rows_kernel<T>, dim3((unsigned) ceil_div(rows * d, 256)), dim3(256), 0, s, X, rows * d, d, c);
+    MI_LAUNCH_CHECK();
+}
+
+template <typename T>
 void launch_row_norms(const T *XT, int64_t n_pad, int64_t d, T *norms, hipStream_t s) {
     hipLaunchKernelGGL(row_norms_kernel<T>, dim3((unsigned) ceil_div(n_pad, 256)), dim3(256), 0, s, XT, n_pad, d,
                        norms);
@@ -199,6 +216,7 @@ void launch_gemv_n(const T *XT, int64_t n_pad, int64_t d, int64_t r0, int64_t r1
 
 #define INST(T)                                                                                                    \
     template void launch_transpose<T>(const T *, int64_t, int64_t, T *, int64_t, hipStream_t);                   \
+    template void launch_shift_rows<T>(T *, int64_t, int64_t, const T *, hipStream_t);                           \
     template void launch_row_norms<T>(const T *, int64_t, int64_t, T *, hipStream_t);                            \
     template void launch_q_dense<T>(kfun<T>, const T *, int64_t, int64_t, int64_t, const T *, T *, hipStream_t); \
     template void launch_kp_finalize<T>(const T *, const T *, const T *, const cg_scalars<T> *, T, T, T, int,    \

@@ -346,16 +346,29 @@ void engine<T>::setup_dense(const T *X, int64_t n_, int64_t d_) {
     // device layout: feature-major XT[d_pad][n_pad] of the first m points; the last point separately
     // (the reference's data_d_ / data_last_d_, gpu_csvm.cpp:142-155, with 64-bit offsets and tile padding)
     XT.alloc(d_pad * n_pad, stream);
+    shifted = kernel == 2 && m > 0;
+    shift_h.assign((size_t) d, T(0));
+    shift.reset();
+    if (shifted) {
+        std::vector<double> sum((size_t) d, 0.0);
+        for (int64_t i = 0; i < m; ++i)
+            for (int64_t k = 0; k < d; ++k) sum[(size_t) k] += (double) X[i * d + k];
+        for (int64_t k = 0; k < d; ++k) shift_h[(size_t) k] = (T) (sum[(size_t) k] / (double) m);
+        shift.alloc(d, stream, false);
+        MI_HIP_CHECK(hipMemcpyAsync(shift.get(), shift_h.data(), sizeof(T) * (size_t) d, hipMemcpyHostToDevice, stream));
+    }
     {
         dev_buf<T> tmp;
         tmp.alloc(std::max<int64_t>(m, 1) * d, stream, false);
         if (m > 0) {
             MI_HIP_CHECK(hipMemcpyAsync(tmp.get(), X, sizeof(T) * (size_t) (m * d), hipMemcpyHostToDevice, stream));
+            if (shifted) launch_shift_rows<T>(tmp.get(), m, d, shift.get(), stream);
             launch_transpose<T>(tmp.get(), m, d, XT.get(), n_pad, stream);
         }
         MI_HIP_CHECK(hipStreamSynchronize(stream));
     }
     xlast_h.assign(X + m * d, X + m * d + d);
+    for (int64_t k = 0; k < d; ++k) xlast_h[(size_t) k] = xlast_h[(size_t) k] - shift_h[(size_t) k];  // x - 0 = x
     xlast.alloc(d_pad, stream);
     MI_HIP_CHECK(hipMemcpyAsync(xlast.get(), xlast_h.data(), sizeof(T) * (size_t) d, hipMemcpyHostToDevice, stream));
     norms.alloc(n_pad, stream);

@@ -80,6 +80,12 @@ struct engine : engine_base {
     int64_t n = 0, d = 0, m = 0, n_pad = 0, d_pad = 0, nb = 0;
     std::vector<T> xlast_h;
     dev_buf<T> XT, norms, xlast;  // dense: XT[d_pad][n_pad]
+    // dense RBF data: the features go to the device as x - shift (in T), shift = the column means of the first m
+    // points, summed in fp64 in row order and rounded to T — the same on every (simulated) rank, rebuilt by every
+    // setup. XT, xlast, xlast_h and every uploaded predict point carry it; the caller never sees it
+    bool shifted = false;
+    std::vector<T> shift_h;
+    dev_buf<T> shift;
     csr_data<T> csr;              // sparse
 
     // work split

@@ -42,6 +42,10 @@ constexpr int kp_dpad() { return 16; }
 template <typename T>
 void launch_transpose(const T *X, int64_t rows, int64_t d, T *XT, int64_t n_pad, hipStream_t s);
 
+// X[i][k] -= c[k] for i < rows, k < d (X row-major [rows][d]): the dense RBF contexts' shift
+template <typename T>
+void launch_shift_rows(T *X, int64_t rows, int64_t d, const T *c, hipStream_t s);
+
 // row norms ||x_i||^2 (sequential fma chain in feature order) for the RBF norm trick
 template <typename T>
 void launch_row_norms(const T *XT, int64_t n_pad, int64_t d, T *norms, hipStream_t s);

@@ -256,6 +256,11 @@ void engine<T>::update_w(const T *alpha_host, T *w_host) {
     update_w_device(a.get());
     if (w_host && d > 0) MI_HIP_CHECK(hipMemcpyAsync(w_host, w.get(), sizeof(T) * (size_t) d, hipMemcpyDeviceToHost, stream));
     MI_HIP_CHECK(hipStreamSynchronize(stream));
+    if (w_host && shifted) {  // sum_i alpha_i x_i of the caller's features: + (sum_i alpha_i) shift
+        double sa = 0.0;
+        for (int64_t i = 0; i < n; ++i) sa += (double) alpha_host[i];
+        for (int64_t k = 0; k < d; ++k) w_host[k] = (T) ((double) w_host[k] + sa * (double) shift_h[(size_t) k]);
+    }
 }
 
 // One class through the paths that do not batch classes: linear (w . z), dense poly / rbf on rocBLAS + epilogue
@@ -323,6 +328,7 @@ void engine<T>::predict_one(const T *alpha_host, T bias, const T *Z, const int64
             const int64_t c = std::min(pc, np - p0);
             for (int64_t p = 0; p < c; ++p) zget(p0 + p, zh.data() + p * d, 1);
             MI_HIP_CHECK(hipMemcpyAsync(zd.get(), zh.data(), sizeof(T) * (size_t) (c * d), hipMemcpyHostToDevice, stream));
+            if (shifted) launch_shift_rows<T>(zd.get(), c, d, shift.get(), stream);
             if (m > 0) MI_BLAS_CHECK(gemm_nn<T>(blas, m, c, d, XT.get(), n_pad, zd.get(), d, gd.get(), ldg));
             hipLaunchKernelGGL(predict_dense_epilogue_kernel<T>, dim3((unsigned) c), dim3(256), 0, stream, kf(), gd.get(),
                                ldg, m, kernel == 2 ? norms.get() : nullptr, a.get(), zd.get(), d, xlast.get(), nlast,
@@ -487,6 +493,7 @@ void engine<T>::predict_tiles(const T *alpha_host, int64_t nclass, int64_t lda, 
                 }
         }
         MI_HIP_CHECK(hipMemcpyAsync(zd.get(), src, sizeof(T) * (size_t) (c * d), hipMemcpyHostToDevice, stream));
+        if (shifted) launch_shift_rows<T>(zd.get(), c, d, shift.get(), stream);
         // columns >= c keep an earlier chunk's points: computed, never stored, and no point's value depends on another's
         launch_transpose<T>(zd.get(), c, d, ztd.get(), pcp, stream);
         if (kernel == 2) launch_row_norms<T>(ztd.get(), pcp, d, nzd.get(), stream);

@@ -749,6 +749,8 @@ void engine<T>::setup_csr(const int64_t *rowptr, const int32_t *col, const void 
     }
     MI_HIP_CHECK(hipSetDevice(device));
     sparse = true;
+    shifted = false;  // sparse data is never shifted: it would lose its sparsity
+    shift.reset();
     n = n_;
     d = d_;
     m = n - 1;

@@ -22,7 +22,7 @@ def test_header_declares_the_entry_points():
     assert re.search(r"PLSSVM_MI_API int plssvm_mi_predict_multi_csr\(plssvm_mi_ctx \*ctx, const void \*ALPHA, "
                      r"int64_t nclass, int64_t lda, const double \*bias, const int64_t \*rowptr, const int32_t \*col, "
                      r"const void \*val, int val_fmt, int64_t np, int64_t d, void \*OUT, int64_t ldo\);", txt)
-    assert re.search(r"int predict_algo;[^}]*\} plssvm_mi_info;", txt)  # the struct's last field
+    assert re.search(r"int predict_algo;[^}]*\} plssvm_mi_info;", txt)  # the struct's last field but one
 
 
 def test_constants_match_the_binding():
@@ -33,7 +33,7 @@ def test_constants_match_the_binding():
     for k in NAMES:
         assert getattr(_abi, "PREDICT_" + k) == got[k], k
     assert _abi.PREDICT_SEG_TILES == got["SEG_TILES"]
-    assert _abi.Info._fields_[-1][0] == "predict_algo"
+    assert [f[0] for f in _abi.Info._fields_[-2:]] == ["predict_algo", "rbf_shift"]  # appended after it, same offset
 
 
 def test_library_exports_the_entry_points():
