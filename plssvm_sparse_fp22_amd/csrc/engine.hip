@@ -540,21 +540,37 @@ void engine<T>::set_q(const T *q_host) {
     }
 }
 
+// ---- the steps of K·p and CG on one right-hand side's state (engine.hpp cg_lane) ----------------------------------
+// sum(p) and sum(q p): the rank-1 parts of Q~ (QA_cost - q_i - q_j) never enter the tiles (sharded: this
+// rank's rows, then the gathered partials of all ranks)
+template <typename T>
+void engine<T>::kp_sums(const T *p, const cg_lane &L, const cg_scalars<T> *status) {
+    launch_dot2<T>(p + v0, nullptr, qf() + v0, p + v0, vn, L.red, status, stream);
+    launch_dot_final<T>(gather_partials(L.red, 3), L.sc, FIN_SP_SQP, 0, nullptr, 0, nullptr, stream, G);
+}
+
+template <typename T>
+void engine<T>::kp_slab_reduce(const cg_lane &L, const cg_scalars<T> *status) {
+    launch_kp_reduce<T>(L.slab, nb, m, t0, t1, kp_wgoff.get(), L.raw, status, stream);
+}
+
+template <typename T>
+void engine<T>::kp_fin(const cg_lane &L, const T *p, T *out, T add, bool overwrite, const cg_scalars<T> *status) {
+    const int flags = (overwrite ? 1 : 0) | ((sim_world > 0 && sim_rank != 0 && !shard) ? 2 : 0);
+    launch_kp_finalize<T>(L.raw + v0, qf() + v0, p + v0, L.sc, QAf(), cost_inv(), add, flags, vn, out + v0, status,
+                          stream);
+}
+
 // out = (overwrite ? 0 : out) + add * Q~ p   — run_device_kernel + device_reduction
 template <typename T>
 void engine<T>::kp_device(const T *p, T *out, T add, bool overwrite, const cg_scalars<T> *status) {
     if (m <= 0) return;
-    cg_scalars<T> *scp = sc.get();
-    // sum(p) and sum(q p): the rank-1 parts of Q~ (QA_cost - q_i - q_j) never enter the tiles (sharded: this
-    // rank's rows, then the gathered partials of all ranks)
-    launch_dot2<T>(p + v0, nullptr, qf() + v0, p + v0, vn, red.get(), status, stream);
-    launch_dot_final<T>(gather_partials(red.get(), 3), scp, FIN_SP_SQP, 0, nullptr, 0, nullptr, stream, G);
+    const cg_lane L = own_lane();
+    kp_sums(p, L, status);
     ctr_now = ctr_active();
     kp_raw(p, status);
     ctr_now = false;
-    const int flags = (overwrite ? 1 : 0) | ((sim_world > 0 && sim_rank != 0 && !shard) ? 2 : 0);
-    launch_kp_finalize<T>(raw.get() + v0, qf() + v0, p + v0, scp, QAf(), cost_inv(), add, flags, vn, out + v0,
-                          status, stream);
+    kp_fin(L, p, out, add, overwrite, status);
 }
 
 template <typename T>
@@ -571,7 +587,7 @@ void engine<T>::kp_raw(const T *p, const cg_scalars<T> *status) {
     } else {
         gather_input(p);
         kp_tiles_now(p, status);
-        launch_kp_reduce<T>(partial.get(), nb, m, t0, t1, kp_wgoff.get(), raw.get(), status, stream);
+        kp_slab_reduce(own_lane(), status);
         if (shard) reduce_scatter_rows(raw.get());
         else allreduce(raw.get(), m);
     }
@@ -627,15 +643,60 @@ void engine<T>::kp_part(const T *p_host, T *out_host, int part) {
 
 // ---- CG: openmp::csvm::solver_CG semantics (src/plssvm/backends/OpenMP/csvm.cpp:82-170) -------------
 template <typename T>
+cg_scalars<T> engine<T>::cg_scalars_init(T eps, bool force) {
+    cg_scalars<T> init{};
+    init.eps2delta0 = eps * eps;
+    init.force = force ? 1 : 0;
+    init.g1[0] = init.g1[1] = init.a1[0] = init.a1[1] = std::numeric_limits<T>::infinity();
+    return init;
+}
+
+// Ad = Q~ v from the K·p's raw (P > 0: summed from P panel slabs) and the v.Ad partials in pd; sharded: with the
+// sum v / sum q v partials the previous step gathered (slot 0)
+template <typename T>
+void engine<T>::cg_fin_dad(const cg_lane &L, const T *v, T *pd, const T *slabs, int64_t P) {
+    const int raw_only = (sim_world > 0 && sim_rank != 0 && !shard) ? 1 : 0;
+    launch_cg_fin_dad<T>(L.raw + v0, slabs, P, m, qf() + v0, v + v0, gathered ? cgp_g.get() : L.cgp, G, QAf(), cost_inv(),
+                         raw_only, vn, L.Ad + v0, pd, L.sc, stream);
+}
+
+// alpha = delta / (d . Ad) (:116); x += alpha d; r = b every 50th iteration, else r -= alpha Ad   (:119-132)
+template <typename T>
+void engine<T>::cg_upd_rr(const cg_lane &L, int reset) {
+    launch_cg_upd_rr<T>(L.x + v0, L.r + v0, L.d + v0, L.Ad + v0, L.b + v0, reset, gather_partials(L.pdad(), 1), G, vn,
+                        L.prr(), L.sc, stream);
+}
+
+template <typename T>
+void engine<T>::cg_rr(const cg_lane &L, const cg_scalars<T> *status) {
+    launch_dot2<T>(L.r + v0, L.r + v0, nullptr, nullptr, vn, L.prr(), status, stream);
+}
+
+// delta = r.r ; delta0   (:92-97)   (sharded: this rank's rows, the ranks' partials gathered)
+template <typename T>
+void engine<T>::cg_delta0(const cg_lane &L) {
+    launch_dot2<T>(L.r + v0, L.r + v0, nullptr, nullptr, vn, L.red, nullptr, stream);
+    launch_dot_final<T>(gather_partials(L.red, 3), L.sc, FIN_DELTA0, 0, L.trace, L.trace_cap, nullptr, stream, G);
+}
+
+// delta = r.r ; stop test ; beta (:135-146); d = beta d + r (:149-151), init: d = r (:97); with sum d / sum q d for
+// the next Q~d (kernel expansion, bfloat16 windows: with the next K·p's w pass, dir_w_fill)
+template <typename T>
+void engine<T>::cg_dir(const cg_lane &L, int init) {
+    dir_w_t<T> wo{};
+    const bool fw = dir_w_fill(wo);
+    launch_cg_dir_sums<T>(L.d + v0, L.r + v0, qf() + v0, init ? nullptr : gather_partials(L.prr(), 2), init ? 1 : G, init,
+                          init ? nullptr : L.trace, init ? 0 : L.trace_cap, vn, L.cgp, L.sc, stream, fw ? &wo : nullptr);
+    w_pre = fw ? L.d : nullptr;
+}
+
+template <typename T>
 void engine<T>::cg_begin(const T *b_host, const T *q_host, T eps, bool force, double *delta0_out, int64_t trace_len) {
     need_data();
     MI_HIP_CHECK(hipSetDevice(device));
     set_q(q_host);
-    cg_scalars<T> init{};
-    init.eps2delta0 = eps * eps;
-    init.force = force ? 1 : 0;
+    const cg_scalars<T> init = cg_scalars_init(eps, force);
     cg1 = cg1_wanted();
-    init.g1[0] = init.g1[1] = init.a1[0] = init.a1[1] = std::numeric_limits<T>::infinity();
     MI_HIP_CHECK(hipMemcpyAsync(sc.get(), &init, sizeof(init), hipMemcpyHostToDevice, stream));
     trace_cap = std::max<int64_t>(trace_len, 1);
     if (trace.size() < trace_cap) trace.alloc(trace_cap, stream);
@@ -644,13 +705,11 @@ void engine<T>::cg_begin(const T *b_host, const T *q_host, T eps, bool force, do
     // x = 1; r = b; r -= Q~x   (csvm.cpp:85-90)
     launch_cg_init<T>(b.get(), m, x.get(), r.get(), stream);
     kp_device(x.get(), r.get(), T(-1), false, nullptr);
-    // delta = r.r ; delta0 ; d = r   (:92-97)   (sharded: this rank's rows, the ranks' partials gathered)
-    launch_dot2<T>(r.get() + v0, r.get() + v0, nullptr, nullptr, vn, red.get(), nullptr, stream);
-    launch_dot_final<T>(gather_partials(red.get(), 3), sc.get(), FIN_DELTA0, 0, trace.get(), trace_cap, nullptr, stream, G);
-    dir_w_t<T> wo{};
-    const bool fw = dir_w_fill(wo);
+    cg_delta0(own_lane());
     if (cg1) {
         // one-reduction CG: d = s = 0, the r.r / sum r / sum q r partials of r0 (set 0) for the first product Q~r
+        dir_w_t<T> wo{};
+        const bool fw = dir_w_fill(wo);
         if (sv.size() < q.size()) sv.alloc(q.size(), stream);
         if (cg1p.size() < 8 * RED_BLOCKS) cg1p.alloc(8 * RED_BLOCKS, stream);  // two [r.u | r.r | r.s | 0] sets
         MI_HIP_CHECK(hipMemsetAsync(dv.get(), 0, sizeof(T) * (size_t) q.size(), stream));
@@ -658,10 +717,7 @@ void engine<T>::cg_begin(const T *b_host, const T *q_host, T eps, bool force, do
         launch_cg1_rsums<T>(r.get() + v0, sv.get() + v0, qf() + v0, vn, cg1p.get(), cgp.get(), sc.get(), stream, fw ? &wo : nullptr);
         w_pre = fw ? r.get() : nullptr;
     } else {
-        // d = r, with sum d / sum q d for the first Q~d
-        launch_cg_dir_sums<T>(dv.get() + v0, r.get() + v0, qf() + v0, nullptr, 1, 1, nullptr, 0, vn, cgp.get(), sc.get(),
-                              stream, fw ? &wo : nullptr);
-        w_pre = fw ? dv.get() : nullptr;
+        cg_dir(own_lane(), 1);
     }
     if (gathered && comm != nullptr) psum_pending = true;  // gathered with the first K·p's collective
     else gather_partials(cgp.get(), 0);
@@ -685,6 +741,43 @@ bool engine<T>::cg1_wanted() const {
     return cg_variant == 1 || (cg_variant == 2 && gathered && G > 1);
 }
 
+// The engine's own Ad = Q~ v with the v.Ad partials in pd (:111-113): v = d, or r for the one-reduction CG (u in Ad)
+template <typename T>
+void engine<T>::cg_product(const T *v, T *pd) {
+    const cg_lane L = own_lane();
+    const cg_scalars<T> *st = L.sc;
+    const bool one_gpu_factored = sparse && factored() && world == 1 && sim_world == 0;
+    const T *slabs = nullptr;
+    int64_t P = 0;
+    bool fin = false;
+    if (sparse_stored() && one_gpu_factored && csr.rb_csr.nblk > 0) {
+        // one GPU, factored sparse linear: CSC pass, then the row-block CSR pass with the finalize and
+        // the v.Ad partials fused (spmv.hpp)
+        spmv_pass_csc(v, st);
+        launch_rowblock_fin<T>(csr.rb_csr, w.get(), d, q.get(), v, L.cgp, QA_cost, cost_inv(), L.Ad, pd, st, stream);
+        fin = true;
+    } else if (one_gpu_factored && csr.spmv_csr.P > 1) {
+        // one GPU, factored sparse linear: the CSR pass's panel slabs are summed by cg_fin_dad
+        spmv_pass_csc(v, st);
+        launch_panel_spmv<T>(csr.spmv_csr, w.get(), d, L.raw, st, stream, 1, 0, false);
+        slabs = csr.spmv_csr.partial.get();
+        P = csr.spmv_csr.P;
+    } else {
+        // offered to the K·p: a path that forms Ad and the partials in its own last kernel sets kp_fin_done
+        const kp_fin_t f{ qf(), v, gathered ? cgp_g.get() : L.cgp, G, QAf(), cost_inv(), L.Ad, pd };
+        kp_fin_req = (sim_world > 0 && sim_rank != 0 && !shard) ? nullptr : &f;
+        kp_fin_done = false;
+        ctr_now = ctr_active();
+        kp_raw(v, st);
+        ctr_now = false;
+        kp_fin_req = nullptr;
+        fin = kp_fin_done;
+        kp_fin_done = false;
+    }
+    flush_psum();  // no collective of the K·p carried it
+    if (!fin) cg_fin_dad(L, v, pd, slabs, P);
+}
+
 // one iteration of the one-reduction CG (blas1.hip cg1_update_kernel): u = Q~r with the finalize forming the r.u
 // partials beside the r.r ones of set `par`, ONE gather of that set, then d, s, x, r and the next partials in one kernel
 template <typename T>
@@ -692,35 +785,7 @@ void engine<T>::cg1_iter(int reset) {
     const cg_scalars<T> *st = sc.get();
     T *psum = cgp.get();
     T *cur = cg1p.get() + (int64_t) cg_par * 4 * RED_BLOCKS, *nxt = cg1p.get() + (int64_t) (cg_par ^ 1) * 4 * RED_BLOCKS;
-    const T *psum_in = gathered ? cgp_g.get() : psum;
-    const int raw_only = (sim_world > 0 && sim_rank != 0 && !shard) ? 1 : 0;
-    const T *slabs = nullptr;
-    int64_t P = 0;
-    bool fin = false;
-    if (sparse_stored() && factored() && world == 1 && sim_world == 0 && csr.rb_csr.nblk > 0) {
-        spmv_pass_csc(r.get(), st);
-        launch_rowblock_fin<T>(csr.rb_csr, w.get(), d, q.get(), r.get(), psum, QA_cost, cost_inv(), Ad.get(), cur, st, stream);
-        fin = true;
-    } else if (sparse && factored() && world == 1 && sim_world == 0 && csr.spmv_csr.P > 1) {
-        spmv_pass_csc(r.get(), st);
-        launch_panel_spmv<T>(csr.spmv_csr, w.get(), d, raw.get(), st, stream, 1, 0, false);
-        slabs = csr.spmv_csr.partial.get();
-        P = csr.spmv_csr.P;
-    } else {
-        const kp_fin_t f{ qf(), r.get(), psum_in, G, QAf(), cost_inv(), Ad.get(), cur };
-        kp_fin_req = raw_only ? nullptr : &f;
-        kp_fin_done = false;
-        ctr_now = ctr_active();
-        kp_raw(r.get(), st);
-        ctr_now = false;
-        kp_fin_req = nullptr;
-        fin = kp_fin_done;
-        kp_fin_done = false;
-    }
-    flush_psum();
-    if (!fin)
-        launch_cg_fin_dad<T>(raw.get() + v0, slabs, P, m, qf() + v0, r.get() + v0, psum_in, G, QAf(), cost_inv(), raw_only, vn,
-                             Ad.get() + v0, cur, sc.get(), stream);
+    cg_product(r.get(), cur);
     // the one collective of the iteration: [r.u | r.r] partials of every rank
     const T *pset = gather_partials(cur, 1, 4 * RED_BLOCKS);
     dir_w_t<T> wo{};
@@ -745,58 +810,16 @@ void engine<T>::cg_iter(int reset) {
         cg1_iter(reset);
         return;
     }
-    const cg_scalars<T> *st = sc.get();
-    T *psum = cgp.get(), *pdad = psum + 2 * RED_BLOCKS, *prr = psum + 4 * RED_BLOCKS;
-    // sharded: the partials the previous step gathered (slot 0: sum d / sum q d)
-    const T *psum_in = gathered ? cgp_g.get() : psum;
-    const int raw_only = (sim_world > 0 && sim_rank != 0 && !shard) ? 1 : 0;
-    // Ad = Q~ d (:111-113); alpha = delta / (d . Ad) (:116) in the next kernel
-    const T *slabs = nullptr;
-    int64_t P = 0;
-    if (sparse_stored() && factored() && world == 1 && sim_world == 0 && csr.rb_csr.nblk > 0) {
-        // one GPU, factored sparse linear: CSC pass, then the row-block CSR pass with the finalize and
-        // the d.Ad partials fused (spmv.hpp)
-        spmv_pass_csc(dv.get(), st);
-        launch_rowblock_fin<T>(csr.rb_csr, w.get(), d, q.get(), dv.get(), psum, QA_cost, cost_inv(), Ad.get(), pdad, st,
-                               stream);
-    } else if (sparse && factored() && world == 1 && sim_world == 0 && csr.spmv_csr.P > 1) {
-        // one GPU, factored sparse linear: the CSR pass's panel slabs are summed by cg_fin_dad
-        spmv_pass_csc(dv.get(), st);
-        launch_panel_spmv<T>(csr.spmv_csr, w.get(), d, raw.get(), st, stream, 1, 0, false);
-        slabs = csr.spmv_csr.partial.get();
-        P = csr.spmv_csr.P;
-    } else {
-        const kp_fin_t fin{ qf(), dv.get(), psum_in, G, QAf(), cost_inv(), Ad.get(), pdad };
-        kp_fin_req = raw_only ? nullptr : &fin;
-        kp_fin_done = false;
-        ctr_now = ctr_active();
-        kp_raw(dv.get(), st);
-        ctr_now = false;
-        kp_fin_req = nullptr;
+    const cg_lane L = own_lane();
+    cg_product(L.d, L.pdad());
+    cg_upd_rr(L, reset);
+    if (reset) {  // r = b - Q~x (:119-132)
+        kp_device(L.x, L.r, T(-1), false, L.sc);
+        cg_rr(L, L.sc);
     }
-    flush_psum();  // no collective of the K·p carried it
-    if (kp_fin_done) {
-        kp_fin_done = false;  // the K·p's last kernel formed Ad and the d.Ad partials
-    } else if (!(sparse_stored() && factored() && world == 1 && sim_world == 0 && csr.rb_csr.nblk > 0)) {
-        launch_cg_fin_dad<T>(raw.get() + v0, slabs, P, m, qf() + v0, dv.get() + v0, psum_in, G, QAf(), cost_inv(),
-                             raw_only, vn, Ad.get() + v0, pdad, sc.get(), stream);
-    }
-    // x += alpha d; r = b - Q~x every 50th iteration, else r -= alpha Ad   (:119-132)
-    launch_cg_upd_rr<T>(x.get() + v0, r.get() + v0, dv.get() + v0, Ad.get() + v0, b.get() + v0, reset,
-                        gather_partials(pdad, 1), G, vn, prr, sc.get(), stream);
-    if (reset) {
-        kp_device(x.get(), r.get(), T(-1), false, st);
-        launch_dot2<T>(r.get() + v0, r.get() + v0, nullptr, nullptr, vn, prr, st, stream);
-    }
-    // delta = r.r ; stop test ; beta (:135-146); d = beta d + r (:149-151), with sum d / sum q d
-    // (kernel expansion, bfloat16 windows: with the next K·p's w pass, dir_w_fill)
-    dir_w_t<T> wo{};
-    const bool fw = dir_w_fill(wo);
-    launch_cg_dir_sums<T>(dv.get() + v0, r.get() + v0, qf() + v0, gather_partials(prr, 2), G, 0, trace.get(), trace_cap,
-                          vn, psum, sc.get(), stream, fw ? &wo : nullptr);
-    w_pre = fw ? dv.get() : nullptr;
+    cg_dir(L, 0);
     if (gathered && comm != nullptr) psum_pending = true;  // gathered with the next K·p's first collective
-    else gather_partials(psum, 0);
+    else gather_partials(L.cgp, 0);
 }
 
 // Iteration blocks of CG_RESET (the reset period) starting at a multiple of it are replayed from one
@@ -905,24 +928,27 @@ void engine<T>::cg_result(T *x_out, double *trace_out, int64_t trace_len, int64_
     }
 }
 
+// batches of iterations between host polls (kernels after convergence exit at entry): 4, 8, 16,
+// then up to the first reset, then whole CG_RESET blocks (one captured graph each in the single solve)
+template <typename T>
+int64_t engine<T>::poll_batch(int64_t done, int64_t imax, int64_t &batch) {
+    const int64_t ns = std::min<int64_t>(done < CG_RESET ? std::min<int64_t>(batch, CG_RESET - done) : CG_RESET, imax - done);
+    batch *= 2;
+    return ns;
+}
+
 template <typename T>
 void engine<T>::solve_cg(const T *b_host, const T *q_host, int64_t imax, T eps, T *x_out, double *trace_out,
                          int64_t *iters) {
     if (imax < 0) throw mi_error(-1, "imax must be >= 0");
     cg_begin(b_host, q_host, eps, false, nullptr, imax + 1);
     bool conv = false;
-    int64_t it = 0;
-    // batches of iterations between host polls (kernels after convergence exit at entry): 4, 8, 16,
-    // then up to the first reset, then whole CG_RESET blocks (one captured graph each)
-    int64_t batch = 4;
+    int64_t it = 0, batch = 4;
     std::vector<double> seg;
     while (!conv && run < imax) {
-        const int64_t ns = std::min<int64_t>(run < CG_RESET ? std::min<int64_t>(batch, CG_RESET - run) : CG_RESET,
-                                             imax - run);
         const int64_t first = it;
         const auto t0 = std::chrono::steady_clock::now();
-        cg_step(ns, conv, it);
-        batch *= 2;
+        cg_step(poll_batch(run, imax, batch), conv, it);
         if (progress != nullptr && it > first) {
             // the batch's residuals delta_first .. delta_it (the iterations' "Start Iteration" lines,
             // OpenMP/csvm.cpp:115-117), the stop target and the batch's wall time
@@ -933,6 +959,16 @@ void engine<T>::solve_cg(const T *b_host, const T *q_host, int64_t imax, T eps, 
         }
     }
     cg_result(x_out, trace_out, imax + 1, iters);
+}
+
+template <typename T>
+void engine<T>::learn_tail(const T *y, const T *q_host, T *alpha, double *bias_out) const {
+    T s = 0, qa = 0;
+    for (int64_t i = 0; i < m; ++i) s += alpha[i];
+    for (int64_t i = 0; i < m; ++i) qa = std::fma(q_host[i], alpha[i], qa);
+    const T bias = y[m] + QA_cost * s - qa;  // (:257)
+    alpha[m] = -s;                           // (:258)
+    if (bias_out) *bias_out = (double) bias;
 }
 
 // csvm<T>::learn (src/plssvm/csvm.cpp:207-267)
@@ -946,12 +982,7 @@ void engine<T>::learn(const T *y, int64_t imax, T eps, T *alpha_out, double *bia
     for (int64_t i = 0; i < m; ++i) bh[i] = y[i] - y[m];  // b = y[0..m) - y[m]   (:238-239)
     if (imax < 0) imax = d;                                // solver_CG(b, num_features_, ...)  (:256)
     solve_cg(bh.data(), nullptr, imax, eps, alpha_out, trace_out, iters);
-    T s = 0, qa = 0;
-    for (int64_t i = 0; i < m; ++i) s += alpha_out[i];
-    for (int64_t i = 0; i < m; ++i) qa = std::fma(qh[i], alpha_out[i], qa);
-    const T bias = y[m] + QA_cost * s - qa;  // (:257)
-    alpha_out[m] = -s;                       // (:258)
-    if (bias_out) *bias_out = (double) bias;
+    learn_tail(y, qh.data(), alpha_out, bias_out);
 }
 
 // time_kp's cache eviction: reads n 16-byte words (their contents are never used; the sink is written only
@@ -1033,13 +1064,21 @@ void engine<T>::time_kp(int reps, double *ms_kp, double *ms_dom) {
 // ---- several right-hand sides over one pass of the tiles (engine.hpp "lanes") -------------------
 
 // The batched path: the pairwise tile path on one rank with the reference recurrence. There G = 1, v0 = 0, vn = m,
-// no collective, no centered finalize and no w pass riding with the direction update, which is what the lane code
-// below relies on. Everything else runs the right-hand sides one after another through the single-vector code.
+// no collective, no centered finalize and no w pass riding with the direction update, so the steps (kp_sums ..
+// cg_dir) launch on a pool lane exactly what they launch for the single solve there (need_pool). Everything else
+// runs the right-hand sides one after another through the single-vector code.
 template <typename T>
 bool engine<T>::multi_batched() const {
     const bool tiles_path = !factored() && (!sparse || csr.dense_on);
     return have_data && tiles_path && m > 0 && kp_wgs > 0 && world == 1 && comm == nullptr && xchg == nullptr &&
            sim_world == 0 && !shard && !cg1_wanted() && multi_opt != 1;
+}
+
+template <typename T>
+void engine<T>::need_pool() {
+    dir_w_t<T> wo{};
+    if (lanes.width < 2 || !multi_batched() || v0 != 0 || vn != m || G != 1 || gathered || ctr_active() || dir_w_fill(wo))
+        throw mi_error(-6, "the batched path was entered on a setup it does not cover");
 }
 
 template <typename T>
@@ -1097,62 +1136,44 @@ void engine<T>::tiles_multi(int kind, int c0, int nvec, bool flags) {
                              kcache_valid ? kcache_tiles : 0, kdesc.get());
 }
 
-// kp_device's first half for p = lane c's x0 = 1 on the engine's own buffers: sum p, sum q p in sc, the pairwise
-// part in raw. The same for every right-hand side, so one product serves a whole group; with no stop flag it also
-// fills an unfilled tile cache (kp_tiles_now).
+// kp_device for lanes [c0, c0 + nvec) with one pass over the tiles (engine.hpp)
 template <typename T>
-void engine<T>::multi_first_product(int c) {
-    const T *x0 = lane_v(LV_X, c);
-    MI_HIP_CHECK(hipMemsetAsync(sc.get(), 0, sizeof(cg_scalars<T>), stream));
-    launch_dot2<T>(x0, nullptr, qf(), x0, m, red.get(), nullptr, stream);
-    launch_dot_final<T>(red.get(), sc.get(), FIN_SP_SQP, 0, nullptr, 0, nullptr, stream, 1);
-    kp_raw(x0, nullptr);
+void engine<T>::kp_lanes(int kin, int kout, int c0, int nvec, T add, bool overwrite, bool flags, bool then_rr) {
+    for (int c = c0; c < c0 + nvec; ++c) {
+        const cg_lane L = pool_lane(c);
+        kp_sums(lane_v(kin, c), L, flags ? L.sc : nullptr);
+    }
+    tiles_multi(kin, c0, nvec, flags);
+    for (int c = c0; c < c0 + nvec; ++c) {
+        const cg_lane L = pool_lane(c);
+        const cg_scalars<T> *st = flags ? L.sc : nullptr;
+        kp_slab_reduce(L, st);
+        kp_fin(L, lane_v(kin, c), lane_v(kout, c), add, overwrite, st);
+        if (then_rr) cg_rr(L, st);
+    }
 }
 
-// cg_iter for nvec lanes: one batched tile launch on the direction vectors, then cg_iter's launches per lane
+// cg_iter for nvec lanes: one batched tile launch on the direction vectors, then cg_iter's steps per lane
 template <typename T>
 void engine<T>::cg_iter_multi(int nvec, int reset) {
     tiles_multi(LV_D, 0, nvec, true);
     for (int c = 0; c < nvec; ++c) {
-        cg_scalars<T> *st = lanes.sc.get() + c;
-        T *psum = lane_cgp(c), *pdad = psum + 2 * RED_BLOCKS, *prr = psum + 4 * RED_BLOCKS;
-        launch_kp_reduce<T>(lanes.slab.get() + (int64_t) c * lanes.sstride, nb, m, t0, t1, kp_wgoff.get(),
-                            lane_v(LV_RAW, c), st, stream);
-        launch_cg_fin_dad<T>(lane_v(LV_RAW, c), nullptr, 0, m, qf(), lane_v(LV_D, c), psum, 1, QAf(), cost_inv(), 0, m,
-                             lane_v(LV_AD, c), pdad, st, stream);
-        launch_cg_upd_rr<T>(lane_v(LV_X, c), lane_v(LV_R, c), lane_v(LV_D, c), lane_v(LV_AD, c), lane_v(LV_B, c), reset,
-                            pdad, 1, m, prr, st, stream);
+        const cg_lane L = pool_lane(c);
+        kp_slab_reduce(L, L.sc);
+        cg_fin_dad(L, L.d, L.pdad(), nullptr, 0);
+        cg_upd_rr(L, reset);
     }
-    if (reset) {  // r = b - Q~x: kp_device on the x vectors, one pass over the tiles
-        for (int c = 0; c < nvec; ++c) {
-            cg_scalars<T> *st = lanes.sc.get() + c;
-            launch_dot2<T>(lane_v(LV_X, c), nullptr, qf(), lane_v(LV_X, c), m, lane_red(c), st, stream);
-            launch_dot_final<T>(lane_red(c), st, FIN_SP_SQP, 0, nullptr, 0, nullptr, stream, 1);
-        }
-        tiles_multi(LV_X, 0, nvec, true);
-        for (int c = 0; c < nvec; ++c) {
-            cg_scalars<T> *st = lanes.sc.get() + c;
-            launch_kp_reduce<T>(lanes.slab.get() + (int64_t) c * lanes.sstride, nb, m, t0, t1, kp_wgoff.get(),
-                                lane_v(LV_RAW, c), st, stream);
-            launch_kp_finalize<T>(lane_v(LV_RAW, c), qf(), lane_v(LV_X, c), st, QAf(), cost_inv(), T(-1), 0, m,
-                                  lane_v(LV_R, c), st, stream);
-            launch_dot2<T>(lane_v(LV_R, c), lane_v(LV_R, c), nullptr, nullptr, m, lane_cgp(c) + 4 * RED_BLOCKS, st, stream);
-        }
-    }
-    for (int c = 0; c < nvec; ++c)
-        launch_cg_dir_sums<T>(lane_v(LV_D, c), lane_v(LV_R, c), qf(), lane_cgp(c) + 4 * RED_BLOCKS, 1, 0,
-                              lanes.trace.get() + (int64_t) c * lanes.trace_cap, lanes.trace_cap, m, lane_cgp(c),
-                              lanes.sc.get() + c, stream);
+    if (reset) kp_lanes(LV_X, LV_R, 0, nvec, T(-1), false, true, true);  // r = b - Q~x, then its r.r
+    for (int c = 0; c < nvec; ++c) cg_dir(pool_lane(c), 0);
 }
 
 // solve_cg for nvec <= width right-hand sides (B[c * ld + i]) as lanes 0 .. nvec - 1; q is set
 template <typename T>
 void engine<T>::solve_cg_group(const T *B, int nvec, int64_t ld, int64_t imax, T eps, T *X_out, double *trace_out,
                                int64_t *iters) {
+    need_pool();
     // cg_begin per lane
-    cg_scalars<T> init{};
-    init.eps2delta0 = eps * eps;
-    init.g1[0] = init.g1[1] = init.a1[0] = init.a1[1] = std::numeric_limits<T>::infinity();
+    const cg_scalars<T> init = cg_scalars_init(eps, false);
     const std::vector<cg_scalars<T>> inits((size_t) nvec, init);
     MI_HIP_CHECK(hipMemcpyAsync(lanes.sc.get(), inits.data(), sizeof(init) * (size_t) nvec, hipMemcpyHostToDevice, stream));
     const int64_t cap = imax + 1;
@@ -1166,26 +1187,25 @@ void engine<T>::solve_cg_group(const T *B, int nvec, int64_t ld, int64_t imax, T
         MI_HIP_CHECK(hipMemcpyAsync(lane_v(LV_B, c), B + c * ld, sizeof(T) * (size_t) m, hipMemcpyHostToDevice, stream));
         launch_cg_init<T>(lane_v(LV_B, c), m, lane_v(LV_X, c), lane_v(LV_R, c), stream);  // x = 1; r = b
     }
-    multi_first_product(0);  // r -= Q~x: x0 is the same for every lane, so is the product
+    // r -= Q~x: x0 = 1 is the same for every lane, so kp_device's first half runs once, on the engine's own buffers
+    // (sum p, sum q p in sc, the pairwise part in raw; with no stop flag it also fills an unfilled tile cache)
+    MI_HIP_CHECK(hipMemsetAsync(sc.get(), 0, sizeof(cg_scalars<T>), stream));
+    kp_sums(lane_v(LV_X, 0), own_lane(), nullptr);
+    kp_raw(lane_v(LV_X, 0), nullptr);
     for (int c = 0; c < nvec; ++c) {
-        cg_scalars<T> *st = lanes.sc.get() + c;
-        launch_kp_finalize<T>(raw.get(), qf(), lane_v(LV_X, c), sc.get(), QAf(), cost_inv(), T(-1), 0, m, lane_v(LV_R, c),
-                              nullptr, stream);
-        launch_dot2<T>(lane_v(LV_R, c), lane_v(LV_R, c), nullptr, nullptr, m, lane_red(c), nullptr, stream);
-        launch_dot_final<T>(lane_red(c), st, FIN_DELTA0, 0, lanes.trace.get() + (int64_t) c * lanes.trace_cap,
-                            lanes.trace_cap, nullptr, stream, 1);
-        launch_cg_dir_sums<T>(lane_v(LV_D, c), lane_v(LV_R, c), qf(), nullptr, 1, 1, nullptr, 0, m, lane_cgp(c), st, stream);
+        const cg_lane L = pool_lane(c);
+        kp_fin(own_lane(), L.x, L.r, T(-1), false, nullptr);
+        cg_delta0(L);
+        cg_dir(L, 1);
     }
-    // solve_cg's polled batches: 4, 8, 16, then up to the first reset, then blocks of CG_RESET; a converged lane's
-    // kernels leave at entry, the group stops when every lane has converged
+    // solve_cg's polled batches; a converged lane's kernels leave at entry, the group stops when every lane has
+    // converged
     std::vector<cg_scalars<T>> h((size_t) nvec);
     int64_t done = 0, batch = 4;
     bool conv = false;
     while (!conv && done < imax) {
-        const int64_t ns = std::min<int64_t>(done < CG_RESET ? std::min<int64_t>(batch, CG_RESET - done) : CG_RESET,
-                                             imax - done);
+        const int64_t ns = poll_batch(done, imax, batch);
         for (int64_t s = 0; s < ns; ++s, ++done) cg_iter_multi(nvec, done % CG_RESET == CG_RESET - 1 ? 1 : 0);
-        batch *= 2;
         MI_HIP_CHECK(hipMemcpyAsync(h.data(), lanes.sc.get(), sizeof(init) * (size_t) nvec, hipMemcpyDeviceToHost, stream));
         MI_HIP_CHECK(hipStreamSynchronize(stream));
         conv = true;
@@ -1241,6 +1261,7 @@ void engine<T>::kp_multi(const T *q_host, const T *P, T *RET, int64_t nrhs, int6
         return;
     }
     set_q(q_host);
+    need_pool();
     cg_active = false;
     for (int64_t c0 = 0; c0 < nrhs; c0 += W) {
         const int nvec = (int) std::min<int64_t>(W, nrhs - c0);
@@ -1255,17 +1276,7 @@ void engine<T>::kp_multi(const T *q_host, const T *P, T *RET, int64_t nrhs, int6
             kp_device(lane_v(LV_D, 0), lane_v(LV_R, 0), add, false, nullptr);
             first = 1;
         }
-        for (int c = first; c < nvec; ++c) {
-            launch_dot2<T>(lane_v(LV_D, c), nullptr, qf(), lane_v(LV_D, c), m, lane_red(c), nullptr, stream);
-            launch_dot_final<T>(lane_red(c), lanes.sc.get() + c, FIN_SP_SQP, 0, nullptr, 0, nullptr, stream, 1);
-        }
-        if (nvec > first) tiles_multi(LV_D, first, nvec - first, false);
-        for (int c = first; c < nvec; ++c) {
-            launch_kp_reduce<T>(lanes.slab.get() + (int64_t) c * lanes.sstride, nb, m, t0, t1, kp_wgoff.get(),
-                                lane_v(LV_RAW, c), nullptr, stream);
-            launch_kp_finalize<T>(lane_v(LV_RAW, c), qf(), lane_v(LV_D, c), lanes.sc.get() + c, QAf(), cost_inv(), add, 0, m,
-                                  lane_v(LV_R, c), nullptr, stream);
-        }
+        if (nvec > first) kp_lanes(LV_D, LV_R, first, nvec - first, add, false, false);
         for (int c = 0; c < nvec; ++c)
             MI_HIP_CHECK(hipMemcpyAsync(RET + (c0 + c) * ld, lane_v(LV_R, c), sizeof(T) * (size_t) m, hipMemcpyDeviceToHost, stream));
         MI_HIP_CHECK(hipStreamSynchronize(stream));
@@ -1286,15 +1297,8 @@ void engine<T>::learn_multi(const T *Y, int64_t nclass, int64_t ldy, int64_t ima
         for (int64_t i = 0; i < m; ++i) bh[(size_t) (c * ldy + i)] = Y[c * ldy + i] - Y[c * ldy + m];  // b = y - y_m
     if (imax < 0) imax = d;
     solve_cg_multi(bh.data(), nclass, ldy, nullptr, imax, eps, alpha_out, trace_out, iters);
-    for (int64_t c = 0; c < nclass; ++c) {
-        const T *y = Y + c * ldy;
-        T *alpha = alpha_out + c * ldy;
-        T s = 0, qa = 0;
-        for (int64_t i = 0; i < m; ++i) s += alpha[i];
-        for (int64_t i = 0; i < m; ++i) qa = std::fma(qh[i], alpha[i], qa);
-        alpha[m] = -s;
-        if (bias_out) bias_out[c] = (double) (y[m] + QA_cost * s - qa);
-    }
+    for (int64_t c = 0; c < nclass; ++c)
+        learn_tail(Y + c * ldy, qh.data(), alpha_out + c * ldy, bias_out ? bias_out + c : nullptr);
 }
 
 // time_kp's K·p time for the batched product of nrhs resident vectors (groups of at most the width; one at a time
@@ -1307,6 +1311,7 @@ void engine<T>::time_kp_multi(int64_t nrhs, int reps, double *ms_kp) {
     MI_HIP_CHECK(hipSetDevice(device));
     if (reps < 1) reps = 1;
     const int W = multi_lanes();
+    if (W >= 2) need_pool();
     cg_active = false;
     std::vector<T> ph(std::max<int64_t>(m, 1));
     for (int64_t i = 0; i < m; ++i) ph[i] = T(1) + T((i * 2654435761ull) % 1000) / T(1000);
@@ -1322,20 +1327,8 @@ void engine<T>::time_kp_multi(int64_t nrhs, int reps, double *ms_kp) {
             for (int64_t c = 0; c < nrhs; ++c) kp_device(p0, ret.get(), T(1), true, nullptr);
             return;
         }
-        for (int64_t c0 = 0; c0 < nrhs; c0 += W) {
-            const int nvec = (int) std::min<int64_t>(W, nrhs - c0);
-            for (int c = 0; c < nvec; ++c) {
-                launch_dot2<T>(lane_v(LV_D, c), nullptr, qf(), lane_v(LV_D, c), m, lane_red(c), nullptr, stream);
-                launch_dot_final<T>(lane_red(c), lanes.sc.get() + c, FIN_SP_SQP, 0, nullptr, 0, nullptr, stream, 1);
-            }
-            tiles_multi(LV_D, 0, nvec, false);
-            for (int c = 0; c < nvec; ++c) {
-                launch_kp_reduce<T>(lanes.slab.get() + (int64_t) c * lanes.sstride, nb, m, t0, t1, kp_wgoff.get(),
-                                    lane_v(LV_RAW, c), nullptr, stream);
-                launch_kp_finalize<T>(lane_v(LV_RAW, c), qf(), lane_v(LV_D, c), lanes.sc.get() + c, QAf(), cost_inv(), T(1), 1,
-                                      m, lane_v(LV_R, c), nullptr, stream);
-            }
-        }
+        for (int64_t c0 = 0; c0 < nrhs; c0 += W)
+            kp_lanes(LV_D, LV_R, 0, (int) std::min<int64_t>(W, nrhs - c0), T(1), true, false);
     };
     product();  // warm-up
     hipEvent_t e0, e1;

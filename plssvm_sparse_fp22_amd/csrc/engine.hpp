@@ -167,7 +167,7 @@ struct engine : engine_base {
     static constexpr int CG_RESET = 50;  // r = b - Q~x every 50th iteration (csvm.cpp:119-132)
     hipGraphExec_t cg_graph = nullptr;   // one captured block of CG_RESET iterations (graph_block)
     // a CG iteration's finalize (Ad, d.Ad partials) offered to the K·p: a path that can form it in its own last
-    // kernel (the kernel expansion's combine) does so and sets kp_fin_done; cg_iter launches it otherwise
+    // kernel (the kernel expansion's combine) does so and sets kp_fin_done; cg_product launches it otherwise
     struct kp_fin_t {
         const T *q, *d, *psum;
         int G;
@@ -188,7 +188,7 @@ struct engine : engine_base {
     T ctr_kmm = 0;         // k(x_m, x_m) as generate_q's QA_cost has it
     bool ctr_ok = false;   // the vectors are built and finite (PLSSVM_MI_CTR=0: never)
     bool q_gen = false;    // the device q is the engine's own k(x_i, x_m)
-    bool ctr_now = false;  // set by kp_device / cg_iter around their K·p: the expansion drops its separable base
+    bool ctr_now = false;  // set by kp_device / cg_product around their K·p: the expansion drops its separable base
     std::vector<T> q_gen_h;
     bool ctr_active() const;
     const T *qf() const { return ctr_active() ? ctr_h.get() : q.get(); }
@@ -223,6 +223,53 @@ struct engine : engine_base {
     void kp_raw(const T *p, const cg_scalars<T> *status);  // raw = the pairwise / sparse part of Q~ p
     void kp_host(const T *q_host, const T *p, T *ret_host, T add);
 
+    // ---- one right-hand side's device state, and the steps of K·p and CG on it ----
+    // A non-owning view: the engine's own vectors (own_lane: the single solve) or lane c of the pool below
+    // (pool_lane). The single solve and a batched group are the same step functions on different views.
+    struct cg_lane {
+        T *x, *r, *d, *Ad, *b, *raw;
+        T *cgp;   // 6 RED_BLOCKS: sum d / sum q d, then d.Ad, then r.r
+        T *red;   // 2 RED_BLOCKS: the K·p sums and delta0
+        T *slab;  // tile records of the last K·p (tile path)
+        cg_scalars<T> *sc;
+        double *trace;
+        int64_t trace_cap;
+        T *pdad() const { return cgp + 2 * RED_BLOCKS; }
+        T *prr() const { return cgp + 4 * RED_BLOCKS; }
+    };
+    cg_lane own_lane() const {
+        return { x.get(), r.get(), dv.get(), Ad.get(), b.get(), raw.get(), cgp.get(), red.get(), partial.get(), sc.get(),
+                 trace.get(), trace_cap };
+    }
+    cg_lane pool_lane(int c) const {
+        return { lane_v(LV_X, c), lane_v(LV_R, c), lane_v(LV_D, c), lane_v(LV_AD, c), lane_v(LV_B, c), lane_v(LV_RAW, c),
+                 lane_cgp(c), lane_red(c), lanes.slab.get() + (int64_t) c * lanes.sstride, lanes.sc.get() + c,
+                 lanes.trace.get() + (int64_t) c * lanes.trace_cap, lanes.trace_cap };
+    }
+    // The steps take the rows [v0, v0 + vn), sum the G ranks' partials (gather_partials) and use qf() / QAf() /
+    // dir_w_fill as the single solve needs them in a group, sharded or on the stored sparse paths. For a pool lane
+    // all of that is the identity — multi_batched(): the tile path on one rank, no shard, no simulated rank, the
+    // reference recurrence, so v0 = 0, vn = m, G = 1, gather_partials returns its argument, ctr_active() and
+    // dir_w_fill() are false (need_pool checks it at the batched entry points). status: the stop flag the kernels
+    // leave at, nullptr = none.
+    void kp_sums(const T *p, const cg_lane &L, const cg_scalars<T> *status);  // sum p, sum q p -> L.sc (through L.red)
+    void kp_slab_reduce(const cg_lane &L, const cg_scalars<T> *status);       // L.slab -> L.raw
+    // out = (overwrite ? 0 : out) + add * Q~ p from L.raw and L.sc's sums (a group's shared first product: the
+    // engine's own raw and sc with a pool lane's p and out)
+    void kp_fin(const cg_lane &L, const T *p, T *out, T add, bool overwrite, const cg_scalars<T> *status);
+    // Ad = Q~ v from raw (or P panel slabs) with the v.Ad partials in pd: v = d, pd = pdad (one-reduction CG: r, its set)
+    void cg_fin_dad(const cg_lane &L, const T *v, T *pd, const T *slabs, int64_t P);
+    void cg_product(const T *v, T *pd);  // the engine's own K·p of v on its path, then (or fused with) cg_fin_dad
+    void cg_upd_rr(const cg_lane &L, int reset);                   // alpha; x, r update; r.r partials
+    void cg_rr(const cg_lane &L, const cg_scalars<T> *status);     // r.r partials of an explicit residual
+    void cg_delta0(const cg_lane &L);                              // delta0 = r.r, trace[0]
+    void cg_dir(const cg_lane &L, int init);  // stop test, beta, d = beta d + r (init: d = r); sum d / sum q d
+    static cg_scalars<T> cg_scalars_init(T eps, bool force);
+    // iterations until the next host poll: 4, 8, 16, ... up to the first reset, then blocks of CG_RESET
+    static int64_t poll_batch(int64_t done, int64_t imax, int64_t &batch);
+    // csvm::learn's end (csvm.cpp:257-258): alpha[m] = -sum alpha, bias = y_m + QA_cost sum alpha - q . alpha
+    void learn_tail(const T *y, const T *q_host, T *alpha, double *bias_out) const;
+
     void cg_begin(const T *b_host, const T *q_host, T eps, bool force, double *delta0_out, int64_t trace_len);
     void cg_iter(int reset);
     bool graph_usable() const;
@@ -239,9 +286,11 @@ struct engine : engine_base {
     // The one-vs-all systems of a multi-class problem share Q~ and differ in b, so their CG solves run as lanes: a
     // lane is one right-hand side's device state (x, r, d, Ad, b, raw, its partials, cg_scalars, trace and tile slab).
     // Each iteration makes ONE pass over the tiles for the live lanes' direction vectors (launch_kp_tiles_multi) and
-    // then runs the single solve's own launches per lane on the lane's buffers, so every lane's x, trace and
-    // iteration count are bitwise solve_cg's on that right-hand side alone. The single-solve members above are not
-    // touched by a batched group except sc, red, raw and partial (the shared first product Q~ x0, x0 = 1).
+    // then runs the step functions above on each lane's view (pool_lane) — the very functions cg_begin and cg_iter
+    // run on own_lane() — so every lane's x, trace and iteration count are bitwise solve_cg's on that right-hand
+    // side alone by construction. lane_v / lane_cgp / lane_red and LV_* are for pool_lane and the strided base of the
+    // batched tile launch only. The single-solve members above are not touched by a batched group except sc, red,
+    // raw and partial (the shared first product Q~ x0, x0 = 1).
     // Batched: the pairwise tile path on one rank (multi_batched); everywhere else, and when not even two lanes fit
     // in device memory, the same entry points run the right-hand sides one after another through solve_cg / kp_host.
     struct lane_pool {
@@ -265,8 +314,12 @@ struct engine : engine_base {
     int64_t lane_bytes() const;           // device memory of one lane
     int multi_width_next() const;         // the width the next multi call would use (1: one at a time); allocates nothing
     int multi_lanes();                    // the lanes, allocated at the first call (width halved until it fits)
+    void need_pool();                     // the steps' group / shard / centring handling is the identity here
     void tiles_multi(int kind, int c0, int nvec, bool flags);  // one pass over the tiles for lanes [c0, c0 + nvec)
-    void multi_first_product(int c);      // Q~ x0 of a group, through the single-vector path (fills the tile cache)
+    // vectors `kout` of lanes [c0, c0 + nvec) = (overwrite ? 0 : kout) + add * Q~ (vectors `kin`): kp_sums per lane, one
+    // pass over the tiles, kp_slab_reduce and kp_fin per lane (then_rr: and cg_rr, the reset's r.r of the new
+    // residual); flags: the lanes' stop flags apply
+    void kp_lanes(int kin, int kout, int c0, int nvec, T add, bool overwrite, bool flags, bool then_rr = false);
     void cg_iter_multi(int nvec, int reset);
     void solve_cg_group(const T *B, int nvec, int64_t ld, int64_t imax, T eps, T *X_out, double *trace_out, int64_t *iters);
     void solve_cg_multi(const T *B, int64_t nrhs, int64_t ld, const T *q_host, int64_t imax, T eps, T *X_out,

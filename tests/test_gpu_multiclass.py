@@ -143,14 +143,19 @@ def _reference_learn(setting, imax=IMAX, graph=None):
     caller has set PLSSVM_MI_GRAPH accordingly)."""
     kernel, m, dtype, gamma, cost, eps = SETTINGS[setting]
     _, lab = _data(m, dtype)
-    classes, Y = pm.one_vs_all(lab, DTYPES[dtype])
-    out = []
     with _svm(kernel, m, dtype, gamma, cost, eps) as svm:
-        svm.setup_data_on_device()
-        for k in range(len(classes)):
-            svm.params.labels = Y[k]
-            svm.learn(imax)
-            out.append((svm.alpha.copy(), svm.bias, svm.iters, svm.trace.copy()))
+        return _single_learns(svm, lab, imax)
+
+
+def _single_learns(svm, lab, imax):
+    """(classes, [(alpha, bias, iters, trace) per class]) of learn() on each one-vs-all label vector, on one context."""
+    classes, Y = pm.one_vs_all(lab, svm.dtype)
+    out = []
+    svm.setup_data_on_device()
+    for k in range(len(classes)):
+        svm.params.labels = Y[k]
+        svm.learn(imax)
+        out.append((svm.alpha.copy(), svm.bias, svm.iters, svm.trace.copy()))
     assert all(np.isfinite(o[0]).all() for o in out)
     return classes, out
 
@@ -253,6 +258,46 @@ def test_fallback_on_stored_sparse_data():
         assert info["is_sparse"] == 1 and info["sparse_algo"] != _abi.SPARSE_DENSE
         assert info["multi_width"] == 1
         _assert_learn_equal(svm, (classes, singles))
+
+
+def test_lanes_on_densified_sparse_data():
+    """CSR data densified on the device runs the tile path, so its one-vs-all solves are lanes: m = 300 is three tile
+    rows, six tiles. gamma = 0.1, C = 100, eps = 1e-6: the CPU oracle's iterations per class are 60 / 59 / 59, past the
+    explicit residual of iteration 50."""
+    n, d, imax = 301, 64, 120
+    csr, _ = datagen.sparse_csr(n, d, 8, seed=5, dtype=np.float64)
+    lab = np.random.default_rng(9).integers(0, 3, n) * 2.5
+
+    def ctx():
+        p = pm.Parameter("rbf", gamma=0.1, cost=100.0, epsilon=1e-6)
+        p.csr = csr
+        return pm.CSVM(p, sparse_algo="dense")
+
+    with ctx() as svm:
+        ref = _single_learns(svm, lab, imax)
+    iters = [s[2] for s in ref[1]]
+    assert len(ref[0]) == 3 and 50 < max(iters) < imax, iters
+    with ctx() as svm:
+        svm.learn_multi(lab, imax)
+        info = svm.info()
+        assert info["is_sparse"] == 1 and info["sparse_algo"] == _abi.SPARSE_DENSE
+        assert info["multi_width"] >= 2
+        _assert_learn_equal(svm, ref)
+
+
+def test_time_kp_multi_leaves_the_context_intact():
+    m, dtype = 130, "f64"
+    lab = _data(m, dtype)[1]
+    with _svm("rbf", m, dtype, eps=1e-6) as svm:
+        ref = _single_learns(svm, lab, IMAX)
+    with _svm("rbf", m, dtype, eps=1e-6) as svm:
+        _ready(svm)
+        assert svm.info()["multi_width"] >= 2
+        ms = svm.time_kp_multi(3, reps=2)
+        assert np.isfinite(ms) and ms > 0
+        _check_kp_multi(svm, "rbf", dtype, m, 3)
+        svm.learn_multi(lab, IMAX)
+        _assert_learn_equal(svm, ref)
 
 
 def test_fallback_on_a_simulated_rank():
