@@ -319,14 +319,20 @@ PLSSVM_MI_API int plssvm_mi_predict_csr(plssvm_mi_ctx *ctx, const void *alpha, d
  * buffer or a too small leading dimension: PLSSVM_MI_ERR_ARG (the context stays usable); np == 0 is a no-op.
  * Dense data with the polynomial / rbf kernel runs the fused tile kernel (csrc/predict_tiles.hip): the kernel values
  * of a (support-vector tile, point tile) pair are formed once on MFMA, never written to memory, and multiplied with
- * every class's alpha (up to 8 classes per pass over the tiles). Everything else (the linear w path, sparse data)
- * runs the classes one after another. plssvm_mi_predict_dense / _csr are the nclass = 1 case of these calls.
+ * every class's alpha (up to 8 classes per pass over the tiles). The linear w path and sparse data prepare and
+ * upload the points once per call and serve up to 8 classes per pass over the support vectors: the expansion's
+ * per-point walk and merge, the brute-force sweep's dot products and kernel values, and the linear path's points are
+ * shared, only the products with a class's coefficients run per class, each in the single call's order. The
+ * fallback from the expansion to brute force depends on the points and the model's data alone and is taken for all
+ * classes together. plssvm_mi_predict_dense / _csr are the nclass = 1 case of these calls.
  * Contract: the decision value of (class c, point z) depends only on the model (the support vectors, alpha_c,
  * bias_c, the kernel parameters) and on z. It does not depend on nclass, on the class's position among the
  * classes, on np, on the point's position in the call, on the chunking of the points, or on the run: row c of OUT is
  * BITWISE what plssvm_mi_predict_dense / _csr return for (alpha_c, bias_c), for any subset or order of the points.
  * Environment, read per call: PLSSVM_MI_PRED_GEMM=1 selects the rocBLAS GEMM + epilogue path for dense poly / rbf
- * (once per class; the A/B baseline), PLSSVM_MI_PRED_CHUNK=<points> overrides the number of points per upload. */
+ * (once per class; the A/B baseline), PLSSVM_MI_PRED_CHUNK=<points> overrides the number of points per upload,
+ * PLSSVM_MI_PRED_SEQ=1 runs the classes of the linear and sparse paths one after another, each with its own point
+ * preparation (the A/B baseline of the shared pass; the same bits). */
 PLSSVM_MI_API int plssvm_mi_predict_multi_dense(plssvm_mi_ctx *ctx, const void *ALPHA, int64_t nclass, int64_t lda,
                                                 const double *bias, const void *Z, int64_t np, int64_t d, void *OUT,
                                                 int64_t ldo);
@@ -334,6 +340,9 @@ PLSSVM_MI_API int plssvm_mi_predict_multi_csr(plssvm_mi_ctx *ctx, const void *AL
                                               const double *bias, const int64_t *rowptr, const int32_t *col,
                                               const void *val, int val_fmt, int64_t np, int64_t d, void *OUT,
                                               int64_t ldo);
+/* How the last predict call ran: out[0] = classes served per pass over the support vectors (1 when the classes ran
+ * one after another, 0 before any call), out[1] = number of times the call uploaded the points. */
+PLSSVM_MI_API int plssvm_mi_get_predict_stats(const plssvm_mi_ctx *ctx, int64_t out[2]);
 
 /* plssvm_mi_info.predict_algo: the path the last predict call of the context took */
 #define PLSSVM_MI_PREDICT_NONE 0      /* no predict call yet */

@@ -22,7 +22,7 @@ import numpy as np
 from . import _abi
 from ._abi import BackendError, KERNELS
 from . import io as _io
-from .io import parse_libsvm, parse_model, read_binary, write_binary
+from .io import parse_libsvm, parse_model, read_binary, write_binary, write_model
 
 __all__ = ["Parameter", "CSVM", "BackendError", "parse_libsvm", "parse_model", "read_binary", "write_binary",
            "device_count", "unique_id", "partition", "torch_exchange", "one_vs_all"]
@@ -142,7 +142,8 @@ class Parameter:
         self.val_fmt = _abi.VAL_REAL
         self.labels = None
 
-    def parse_train_file(self, path, sparse=False):
+    def parse_train_file(self, path, sparse=False, multiclass=False):
+        """multiclass: keep the label values as written (learn_multi's classes) instead of their signs."""
         try:
             with open(path, "rb") as f:
                 binary = f.read(8) == _io.BIN_MAGIC
@@ -155,7 +156,7 @@ class Parameter:
             if self.gamma == 0:
                 self.gamma = float(self.real_type.type(1) / self.real_type.type(csr[4]))
             return self
-        X, y = parse_libsvm(path, dtype=self.real_type, sparse=sparse)
+        X, y = parse_libsvm(path, dtype=self.real_type, sparse=sparse, multiclass=multiclass)
         if sparse:
             self.csr, self.data = X, None
             d = X[4]
@@ -434,8 +435,9 @@ class CSVM:
 
     def predict_values_multi(self, points, val_fmt=None, alphas=None, biases=None):
         """Decision values [np][K] of the learn_multi model (or of alphas [K][n], biases [K]) in one call: on dense
-        data with the polynomial / rbf kernel every class shares one pass over the kernel values. Column k is bitwise
-        predict_values with class k's alpha and bias."""
+        data with the polynomial / rbf kernel every class shares one pass over the kernel values; on sparse data and
+        with the linear kernel the points are prepared once and up to 8 classes share each pass over the support
+        vectors. Column k is bitwise predict_values with class k's alpha and bias."""
         alphas = self.alphas if alphas is None else alphas
         biases = self.biases if biases is None else biases
         if alphas is None:
@@ -469,6 +471,13 @@ class CSVM:
     def predict_multi(self, points, val_fmt=None):
         """The class with the largest decision value (the lowest class index on a tie)."""
         return self.classes[np.argmax(self.predict_values_multi(points, val_fmt), axis=1)]
+
+    def predict_stats(self):
+        """[classes served per pass over the support vectors, point uploads] of the last predict call ([0, 0] before
+        any): [min(K, 8), 1] when the classes share the pass, [1, K] when they ran one after another."""
+        out = (ctypes.c_int64 * 2)()
+        self._check(_abi.lib().plssvm_mi_get_predict_stats(self._ctx, out))
+        return [int(out[0]), int(out[1])]
 
     def time_kp_multi(self, nrhs, reps=5):
         a = ctypes.c_double()

@@ -33,7 +33,7 @@ EXPORTS = (
     "plssvm_mi_update_w", "plssvm_mi_predict_dense", "plssvm_mi_predict_csr", "plssvm_mi_setup_coo",
     "plssvm_mi_comm_init_host", "plssvm_mi_kp_part", "plssvm_mi_set_progress", "plssvm_mi_comm_abort",
     "plssvm_mi_kp_multi", "plssvm_mi_solve_cg_multi", "plssvm_mi_learn_multi", "plssvm_mi_time_kp_multi",
-    "plssvm_mi_predict_multi_dense", "plssvm_mi_predict_multi_csr",
+    "plssvm_mi_predict_multi_dense", "plssvm_mi_predict_multi_csr", "plssvm_mi_get_predict_stats",
 )
 OPT_SIM_RANK = 2
 OPT_RBF_FORM = 3
@@ -132,6 +132,7 @@ def _declare(L):
         "plssvm_mi_time_kp_multi": ([P, I64, I, PD], I),
         "plssvm_mi_predict_multi_dense": ([P, P, I64, I64, P, P, I64, I64, P, I64], I),
         "plssvm_mi_predict_multi_csr": ([P, P, I64, I64, P, P, P, P, I, I64, I64, P, I64], I),
+        "plssvm_mi_get_predict_stats": ([P, PI64], I),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

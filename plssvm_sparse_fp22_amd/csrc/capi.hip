@@ -434,6 +434,15 @@ int plssvm_mi_predict_multi_csr(plssvm_mi_ctx *ctx, const void *ALPHA, int64_t n
     });
 }
 
+int plssvm_mi_get_predict_stats(const plssvm_mi_ctx *cctx, int64_t out[2]) {
+    if (!cctx || !out) return PLSSVM_MI_ERR_ARG;
+    auto *ctx = const_cast<plssvm_mi_ctx *>(cctx);
+    return ctx->call([&](auto &e) {
+        out[0] = e.predict_classes_per_pass;
+        out[1] = e.predict_uploads;
+    });
+}
+
 int plssvm_mi_get_info(const plssvm_mi_ctx *cctx, plssvm_mi_info *info) {
     if (!cctx || !info) return PLSSVM_MI_ERR_ARG;
     auto *ctx = const_cast<plssvm_mi_ctx *>(cctx);

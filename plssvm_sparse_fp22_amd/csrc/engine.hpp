@@ -359,10 +359,12 @@ struct engine : engine_base {
                                int sG = 1);  // true: reduced straight into M
     bool expansion_moments_fused() const;  // the moment pass has panel slabs (then its reduce can form S)
     coefs expansion_coefs() const;
-    // predict through the expansion (expand.hip); false: not applicable, predict brute force
-    bool expansion_predict(const T *alpha_dev, T alpha_m, T bias, const int64_t *zr_dev, const int32_t *zc_dev,
-                           const T *zv_dev, int64_t np, int64_t max_nnz_z, double zabs_max, double znorm_max, T nlast,
-                           T *out_dev);
+    // predict nclass models through the expansion (expand.hip), KP_MULTI_W classes per pass over the points; false: not
+    // applicable (a decision for all classes together), predict brute force. alpha_dev [nclass][lda], ab_dev: the
+    // classes' alpha_m, then their biases; out_dev [nclass][ldo]
+    bool expansion_predict(const T *alpha_dev, int64_t lda, int64_t nclass, const T *ab_dev, const int64_t *zr_dev,
+                           const int32_t *zc_dev, const T *zv_dev, int64_t np, int64_t max_nnz_z, double zabs_max,
+                           double znorm_max, T nlast, T *out_dev, int64_t ldo);
     // raw[i] = sum_j k_ij p_j, i < m (with_base = false: only the overlap terms, PLSSVM_MI_PART_OVERLAP)
     void sparse_kp_raw(const T *p, const cg_scalars<T> *status, bool with_base = true);
     void sparse_dominant(const T *p, const cg_scalars<T> *status);  // the dominant sparse kernel
@@ -377,14 +379,18 @@ struct engine : engine_base {
     void predict(const T *alpha_host, T bias, const T *Z, const int64_t *zrowptr, const int32_t *zcol, const void *zval,
                  int zfmt, int64_t np, int64_t dz, T *out);  // predict_multi with nclass = 1
     // nclass models on the context's support vectors: alpha[nclass][lda], bias[nclass], out[nclass][ldo] (host). Dense
-    // data with the polynomial / rbf kernel: predict_tiles, every class in one pass over the kernel values; everything
-    // else: the classes one after another through predict_one. Row c is bitwise the single call with (alpha_c, bias_c)
+    // data with the polynomial / rbf kernel: predict_tiles, every class in one pass over the kernel values. The linear w
+    // path and sparse data: predict_shared, the points prepared once and up to KP_MULTI_W classes per pass over the
+    // support vectors (PLSSVM_MI_PRED_SEQ=1 or PLSSVM_MI_PRED_GEMM=1, read per call: one predict_shared call per
+    // class). Row c is bitwise the single call with (alpha_c, bias_c)
     void predict_multi(const T *alpha_host, int64_t nclass, int64_t lda, const T *bias, const T *Z, const int64_t *zrowptr,
                        const int32_t *zcol, const void *zval, int zfmt, int64_t np, int64_t dz, T *out, int64_t ldo);
     void predict_tiles(const T *alpha_host, int64_t nclass, int64_t lda, const T *bias, const T *Z, const int64_t *zrowptr,
                        const int32_t *zcol, const void *zval, int zfmt, int64_t np, T *out, int64_t ldo);
-    void predict_one(const T *alpha_host, T bias, const T *Z, const int64_t *zrowptr, const int32_t *zcol, const void *zval,
-                     int zfmt, int64_t np, T *out);
+    void predict_shared(const T *alpha_host, int64_t nclass, int64_t lda, const T *bias, const T *Z, const int64_t *zrowptr,
+                        const int32_t *zcol, const void *zval, int zfmt, int64_t np, T *out, int64_t ldo);
+    // plssvm_mi_get_predict_stats: classes per pass over the support vectors and point uploads of the last predict call
+    int64_t predict_classes_per_pass = 0, predict_uploads = 0;
     int predict_algo = 0;  // PLSSVM_MI_PREDICT_*: the path of the last predict call
 
     void allreduce(T *buf, int64_t count);

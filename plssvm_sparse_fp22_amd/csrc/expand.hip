@@ -2827,15 +2827,19 @@ __device__ __forceinline__ double pred_block_sum(double v, double *red) {
     return s;
 }
 
-// one point per workgroup; zr/zc/zv: the points' CSR (columns ascending); S: sum w (device scalar);
-// flag[0] set when a pass held more than PRED_MCAP repeat rows (the caller then recomputes brute force)
-template <typename T>
+// one point per workgroup, nc <= NC classes per launch: the walk, the bitmap, the enumeration and the merge that
+// forms s_iz and the phi sum do not depend on the class and run once; only w_c[i] H_iz, the Horner sum over class
+// c's moments and the closing expression run per class, each in the single-class order (row c is bitwise the
+// nc = 1 launch). zr/zc/zv: the points' CSR (columns ascending); class c: w + c ldw, M + c ldm, S[2 c] (sum w),
+// am[c] (alpha_m) and bias[c], out + c ldo. flag[0] set when a pass held more than PRED_MCAP repeat rows (the
+// caller then recomputes brute force)
+template <typename T, int NC>
 __global__ __launch_bounds__(PRED_NT) void exp_pred_point_kernel(
     const int64_t *__restrict__ zr, const int32_t *__restrict__ zc, const T *__restrict__ zv, const int64_t *__restrict__ colptr,
     const int32_t *__restrict__ crow, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
-    const T *__restrict__ val, const T *__restrict__ w, const T *__restrict__ M, int KM, phi_fn phi, int64_t m,
-    const T *__restrict__ S, const T *__restrict__ xlast, T nlast, T alpha_m, kfun<T> kf, T kappa, T bias,
-    T *__restrict__ out, int *__restrict__ flag) {
+    const T *__restrict__ val, const T *__restrict__ w, int64_t ldw, const T *__restrict__ M, int64_t ldm, int KM,
+    phi_fn phi, int64_t m, const T *__restrict__ S, const T *__restrict__ xlast, T nlast, const T *__restrict__ am,
+    kfun<T> kf, T kappa, const T *__restrict__ bias, int nc, T *__restrict__ out, int64_t ldo, int *__restrict__ flag) {
     __shared__ uint32_t bm[PRED_BMW];
     __shared__ int32_t zcol_s[PRED_ZCAP];
     __shared__ T zval_s[PRED_ZCAP];
@@ -2876,17 +2880,24 @@ __global__ __launch_bounds__(PRED_NT) void exp_pred_point_kernel(
     __syncthreads();
     const T nzz = (T) red[0], dl = (T) red[1];
     const int64_t inc = zoff[nz];
-    // J_z = sum_e z_e (M0 + z_e (M1 + ...)) in the real type's Horner order
-    double js = 0.0;
-    for (int e = tid; e < nz; e += PRED_NT) {
-        const T z = zval_s[e];
-        const T *Mf = M + (int64_t) zcol_s[e] * KM;
-        T h = Mf[KM - 1];
-        for (int k = KM - 2; k >= 0; --k) h = fma(h, z, Mf[k]);
-        js += (double) (h * z);
+    // J_z = sum_e z_e (M0 + z_e (M1 + ...)) in the real type's Horner order, per class
+    double J[NC], hs[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        J[c] = 0.0;
+        hs[c] = 0.0;
+        if (c < nc) {  // uniform
+            double js = 0.0;
+            for (int e = tid; e < nz; e += PRED_NT) {
+                const T z = zval_s[e];
+                const T *Mf = M + c * ldm + (int64_t) zcol_s[e] * KM;
+                T h = Mf[KM - 1];
+                for (int k = KM - 2; k >= 0; --k) h = fma(h, z, Mf[k]);
+                js += (double) (h * z);
+            }
+            J[c] = pred_block_sum<T>(js, red);
+        }
     }
-    const double J = pred_block_sum<T>(js, red);
-    double hs = 0.0;
     const int64_t BMBITS = (int64_t) PRED_BMW * 32;
     for (int64_t R0 = 0; R0 < m; R0 += BMBITS) {
         const int64_t R1 = min(m, R0 + BMBITS);
@@ -2975,19 +2986,17 @@ __global__ __launch_bounds__(PRED_NT) void exp_pred_point_kernel(
                     sphi += phi(a);
                 }
             }
-            hs += (double) w[i] * (phi(sdot) - sphi);
+            const double hiz = phi(sdot) - sphi;
+#pragma unroll
+            for (int c = 0; c < NC; ++c)
+                if (c < nc) hs[c] += (double) w[c * ldw + i] * hiz;
         }
         __syncthreads();
     }
-    const double H = pred_block_sum<T>(hs, red);
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+        if (c < nc) hs[c] = pred_block_sum<T>(hs[c], red);
     if (tid == 0) {
-        double v;
-        if (phi.rbf) {
-            const double ez = exp(-(double) kf.gamma * (double) nzz);
-            v = ez * ((double) S[0] + J + H);
-        } else {
-            v = (double) kappa * (double) S[0] + J + H;
-        }
         // the last training point (kept apart, as the reference's data_last)
         T kl;
         if (kf.kernel == 1) {
@@ -2999,15 +3008,30 @@ __global__ __launch_bounds__(PRED_NT) void exp_pred_point_kernel(
             dist = dist > T(0) ? dist : T(0);
             kl = exp(-kf.gamma * dist);
         }
-        out[p] = (T) (v + (double) (alpha_m * kl)) + bias;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            if (c < nc) {
+                double v;
+                if (phi.rbf) {
+                    const double ez = exp(-(double) kf.gamma * (double) nzz);
+                    v = ez * ((double) S[2 * c] + J[c] + hs[c]);
+                } else {
+                    v = (double) kappa * (double) S[2 * c] + J[c] + hs[c];
+                }
+                out[c * ldo + p] = (T) (v + (double) (am[c] * kl)) + bias[c];
+            }
+        }
     }
 }
 
-// predict through the expansion; false when it does not apply (the caller predicts brute force)
+// predict nclass models through the expansion, at most KP_MULTI_W classes per pass over the points; false when it
+// does not apply (the caller predicts brute force). Every condition depends on the points and the model's data
+// alone, so the decision holds for all classes together. alpha_dev: [nclass][lda]; ab_dev: the classes' alpha_m,
+// then their biases; out_dev: [nclass][ldo]
 template <typename T>
-bool engine<T>::expansion_predict(const T *alpha_dev, T alpha_m, T bias, const int64_t *zr_dev, const int32_t *zc_dev,
-                                  const T *zv_dev, int64_t np, int64_t max_nnz_z, double zabs_max, double znorm_max,
-                                  T nlast, T *out_dev) {
+bool engine<T>::expansion_predict(const T *alpha_dev, int64_t lda, int64_t nclass, const T *ab_dev, const int64_t *zr_dev,
+                                  const int32_t *zc_dev, const T *zv_dev, int64_t np, int64_t max_nnz_z, double zabs_max,
+                                  double znorm_max, T nlast, T *out_dev, int64_t ldo) {
     auto &ex = csr.ex;
     if (!ex.on || kernel == 0 || m <= 0 || max_nnz_z > PRED_ZCAP) return false;
     if (std::getenv("PLSSVM_MI_PRED_BRUTE") != nullptr) return false;
@@ -3016,21 +3040,14 @@ bool engine<T>::expansion_predict(const T *alpha_dev, T alpha_m, T bias, const i
     if (kernel == 2 && 2.0 * std::fabs((double) gamma) * xabs * zabs_max > ex.umax) return false;
     if (kernel == 2 && std::fabs((double) gamma) * znorm_max > (sizeof(T) == 8 ? 300.0 : 40.0)) return false;
     const phi_fn phi = make_phi<T>(kernel, degree, gamma, coef0);
+    const int ncp = (int) std::min<int64_t>(nclass, KP_MULTI_W);  // classes per pass
+    const int64_t ldw = std::max<int64_t>(m, 1), ldm = std::max<int64_t>(d, 1) * ex.KM;
     dev_buf<T> wv, Md, Sd;
-    wv.alloc(std::max<int64_t>(m, 1), stream, false);
-    Md.alloc(std::max<int64_t>(d, 1) * ex.KM, stream, false);
-    Sd.alloc(2, stream);
-    hipLaunchKernelGGL(exp_pred_w_kernel<T>, dim3((unsigned) ceil_div(m, 256)), dim3(256), 0, stream, alpha_dev,
-                       kernel == 2 ? csr.e.get() : nullptr, m, wv.get());
-    MI_LAUNCH_CHECK();
-    launch_dot2<T>(wv.get(), nullptr, nullptr, nullptr, m, red.get(), nullptr, stream);
-    launch_dot_final<T>(red.get(), sc.get(), FIN_PLAIN, 0, nullptr, 0, Sd.get(), stream);
+    wv.alloc(ncp * ldw, stream, false);
+    Md.alloc(ncp * ldm, stream, false);
+    Sd.alloc(2 * ncp, stream);
     coefs cf;
     std::memcpy(cf.c, ex.coef, sizeof(cf.c));
-    if (d > 0)
-        hipLaunchKernelGGL(exp_pred_moments_kernel<T>, dim3((unsigned) ceil_div(d, 4)), dim3(256), 0, stream,
-                           csr.colptr.get(), csr.crow.get(), csr.cval.get(), wv.get(), d, ex.K, ex.KM, cf, Md.get());
-    MI_LAUNCH_CHECK();
     T kappa = 0;
     if (kernel == 1) {
         kappa = 1;
@@ -3038,15 +3055,34 @@ bool engine<T>::expansion_predict(const T *alpha_dev, T alpha_m, T bias, const i
     }
     dev_buf<int> flag;
     flag.alloc(1, stream);
-    hipLaunchKernelGGL(exp_pred_point_kernel<T>, dim3((unsigned) np), dim3(PRED_NT), 0, stream, zr_dev, zc_dev, zv_dev,
-                       csr.colptr.get(), csr.crow.get(), csr.rowptr.get(), csr.col.get(), csr.val.get(), wv.get(),
-                       Md.get(), ex.KM, phi, m, Sd.get(), xlast.get(), nlast, alpha_m, kf(), kappa, bias, out_dev,
-                       flag.get());
-    MI_LAUNCH_CHECK();
-    int hf = 0;
-    MI_HIP_CHECK(hipMemcpyAsync(&hf, flag.get(), sizeof(int), hipMemcpyDeviceToHost, stream));
-    MI_HIP_CHECK(hipStreamSynchronize(stream));
-    return hf == 0;
+    for (int64_t c0 = 0; c0 < nclass; c0 += ncp) {
+        const int nc = (int) std::min<int64_t>(ncp, nclass - c0);
+        // w_c, S_c and M_c per class: O(nnz)
+        for (int c = 0; c < nc; ++c) {
+            T *wc = wv.get() + c * ldw;
+            hipLaunchKernelGGL(exp_pred_w_kernel<T>, dim3((unsigned) ceil_div(m, 256)), dim3(256), 0, stream,
+                               alpha_dev + (c0 + c) * lda, kernel == 2 ? csr.e.get() : nullptr, m, wc);
+            MI_LAUNCH_CHECK();
+            launch_dot2<T>(wc, nullptr, nullptr, nullptr, m, red.get(), nullptr, stream);
+            launch_dot_final<T>(red.get(), sc.get(), FIN_PLAIN, 0, nullptr, 0, Sd.get() + 2 * c, stream);
+            if (d > 0)
+                hipLaunchKernelGGL(exp_pred_moments_kernel<T>, dim3((unsigned) ceil_div(d, 4)), dim3(256), 0, stream,
+                                   csr.colptr.get(), csr.crow.get(), csr.cval.get(), wc, d, ex.K, ex.KM, cf,
+                                   Md.get() + c * ldm);
+            MI_LAUNCH_CHECK();
+        }
+        auto point_kernel = nc == 1 ? exp_pred_point_kernel<T, 1> : exp_pred_point_kernel<T, KP_MULTI_W>;
+        hipLaunchKernelGGL(point_kernel, dim3((unsigned) np), dim3(PRED_NT), 0, stream, zr_dev, zc_dev, zv_dev,
+                           csr.colptr.get(), csr.crow.get(), csr.rowptr.get(), csr.col.get(), csr.val.get(), wv.get(), ldw,
+                           Md.get(), ldm, ex.KM, phi, m, Sd.get(), xlast.get(), nlast, ab_dev + c0, kf(), kappa,
+                           ab_dev + nclass + c0, nc, out_dev + c0 * ldo, ldo, flag.get());
+        MI_LAUNCH_CHECK();
+        int hf = 0;
+        MI_HIP_CHECK(hipMemcpyAsync(&hf, flag.get(), sizeof(int), hipMemcpyDeviceToHost, stream));
+        MI_HIP_CHECK(hipStreamSynchronize(stream));
+        if (hf != 0) return false;  // PRED_MCAP overflow: a property of the points, the same in every pass
+    }
+    return true;
 }
 
 int exp_dot2_built() { return EXP_DOT2 ? 1 : 0; }
@@ -3070,8 +3106,8 @@ void exp_load_code_object() {
     template bool engine<T>::ctr_active() const;                                              \
     template T engine<T>::QAf() const;                                                        \
     template void engine<T>::ctr_setup();                                                     \
-    template bool engine<T>::expansion_predict(const T *, T, T, const int64_t *, const int32_t *, const T *, int64_t, \
-                                               int64_t, double, double, T, T *);
+    template bool engine<T>::expansion_predict(const T *, int64_t, int64_t, const T *, const int64_t *, const int32_t *, \
+                                               const T *, int64_t, int64_t, double, double, T, T *, int64_t);
 INST(float)
 INST(double)
 #undef INST

@@ -17,7 +17,11 @@
 //     fixed order, once per class (no atomics either way: a prediction is bitwise reproducible);
 //   * sparse data: one wave per CSR row and one lane per predict point (64 points per launch); the
 //     chunk's points are densified feature-major (ZT[f][64]) so the per-entry gather is one
-//     coalesced 64-lane read, partial sums per row block, reduced in block order.
+//     coalesced 64-lane read, partial sums per row block, reduced in block order;
+//   * several classes on the linear and sparse paths (predict_shared): the points are prepared and uploaded once,
+//     and a pass over the support vectors serves up to KP_MULTI_W classes — the row's dot product and kernel value
+//     (expansion: the per-point walk and merge, expand.hip) are formed once, only the products with a class's
+//     coefficients run per class, in the single call's order (row c is bitwise the one-class call).
 #include <rocblas/rocblas.h>
 
 #include <algorithm>
@@ -89,33 +93,43 @@ __global__ __launch_bounds__(256) void predict_dense_epilogue_kernel(kfun<T> kf,
     if (threadIdx.x == 0) out[p] = (s + alpha[m] * kval(kf, dl, nlast, nz)) + bias;
 }
 
-// linear: out[p] = w . z_p + bias (the reference's fast path for the linear kernel)
+// linear: out[c][p] = w_c . z_p + bias_c (the reference's fast path for the linear kernel) for the nclass rows of
+// W[nclass][d]; one workgroup per point, each class its own strided chain and block sum
 template <typename T>
-__global__ __launch_bounds__(256) void predict_linear_kernel(const T *__restrict__ w, const T *__restrict__ Z, int64_t d,
-                                                             T bias, T *__restrict__ out) {
+__global__ __launch_bounds__(256) void predict_linear_kernel(const T *__restrict__ W, const T *__restrict__ Z, int64_t d,
+                                                             const T *__restrict__ bias, int64_t nclass, T *__restrict__ out,
+                                                             int64_t ldo) {
     __shared__ T red[4];
     const int64_t p = blockIdx.x;
     const T *z = Z + p * d;
-    T s = 0;
-    for (int64_t k = threadIdx.x; k < d; k += 256) s = fma(w[k], z[k], s);
-    s = block_sum256(s, red);
-    if (threadIdx.x == 0) out[p] = s + bias;
+    for (int64_t c = 0; c < nclass; ++c) {
+        const T *w = W + c * d;
+        T s = 0;
+        for (int64_t k = threadIdx.x; k < d; k += 256) s = fma(w[k], z[k], s);
+        s = block_sum256(s, red);
+        if (threadIdx.x == 0) out[c * ldo + p] = s + bias[c];
+    }
 }
 
-// sparse data: partial[b][lane] = sum_{i in row block b} alpha_i k(x_i, z_lane); ZT = [d][64]
+// sparse data: partial[c][b][lane] = sum_{i in row block b} alpha_c[i] k(x_i, z_lane) for nc <= NC classes
+// (alpha + c lda); ZT = [d][64]. The row's dot product and kernel value are formed once, only the closing fma runs
+// per class (alpha_c[i] is wave-uniform)
 constexpr int PRED_ROWS = 256;  // rows per workgroup
 constexpr int PRED_STEP = 8;    // CSR entries per wave step (gathers in flight)
-template <typename T>
+template <typename T, int NC>
 __global__ __launch_bounds__(256) void predict_csr_kernel(kfun<T> kf, const int64_t *__restrict__ rowptr,
                                                           const int32_t *__restrict__ col, const T *__restrict__ val,
                                                           int64_t m, const T *__restrict__ ZT,
                                                           const T *__restrict__ nzv, const T *__restrict__ norms,
-                                                          const T *__restrict__ alpha, T *__restrict__ partial) {
-    __shared__ T red[4][64];
+                                                          const T *__restrict__ alpha, int64_t lda, int nc,
+                                                          T *__restrict__ partial) {
+    __shared__ T red[NC][4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t r0 = (int64_t) blockIdx.x * PRED_ROWS, r1 = min(m, r0 + PRED_ROWS);
     const T nz = nzv[lane];
-    T acc = 0;
+    T acc[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) acc[c] = 0;
     for (int64_t i = r0 + wave; i < r1; i += 4) {
         T s = 0;
         const int64_t e0 = rowptr[i], e1 = rowptr[i + 1];
@@ -135,11 +149,21 @@ __global__ __launch_bounds__(256) void predict_csr_kernel(kfun<T> kf, const int6
 #pragma unroll
             for (int u = 0; u < PRED_STEP; ++u) s = fma(v[u], g[u], s);
         }
-        acc = fma(alpha[i], kval(kf, s, norms[i], nz), acc);
+        const T k = kval(kf, s, norms[i], nz);
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+            if (c < nc) acc[c] = fma(alpha[c * lda + i], k, acc[c]);
     }
-    red[wave][lane] = acc;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) red[c][wave][lane] = acc[c];
     __syncthreads();
-    if (wave == 0) partial[(int64_t) blockIdx.x * 64 + lane] = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+    if (wave == 0) {
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+            if (c < nc)
+                partial[((int64_t) c * gridDim.x + blockIdx.x) * 64 + lane] =
+                    (red[c][0][lane] + red[c][1][lane]) + (red[c][2][lane] + red[c][3][lane]);
+    }
 }
 
 // ZT[col][p] = z_p[col] and |z_p|^2 (sequential fma in column order: the densified chain with its zero
@@ -160,22 +184,26 @@ __global__ __launch_bounds__(64) void zt_scatter_kernel(const int64_t *__restric
     nz[p] = v;
 }
 
-// out[p] = bias + alpha_m k(x_m, z_p) + sum_b partial[b][p] (block order); one workgroup per point
+// out[c][p] = bias_c + alpha_c[m] k(x_m, z_p) + sum_b partial[c][b][p] (block order) for nc classes; one workgroup
+// per point, x_m . z_p and its kernel value once. am: the classes' alpha_m, bias: their biases
 template <typename T>
 __global__ __launch_bounds__(256) void predict_csr_final_kernel(kfun<T> kf, const T *__restrict__ partial, int64_t nblk,
                                                                 const T *__restrict__ ZT, const T *__restrict__ nzv,
                                                                 int64_t d, const T *__restrict__ xlast, T nlast,
-                                                                const T *__restrict__ alpha, int64_t m, T bias,
-                                                                int64_t np, T *__restrict__ out) {
+                                                                const T *__restrict__ am, const T *__restrict__ bias,
+                                                                int nc, int64_t np, T *__restrict__ out, int64_t ldo) {
     __shared__ T red[4];
     const int p = blockIdx.x;
     T dl = 0;
     for (int64_t k = threadIdx.x; k < d; k += 256) dl = fma(xlast[k], ZT[k * 64 + p], dl);
     dl = block_sum256(dl, red);
-    if (threadIdx.x == 0) {
-        T s = 0;
-        for (int64_t b = 0; b < nblk; ++b) s += partial[b * 64 + p];
-        if (p < np) out[p] = (s + alpha[m] * kval(kf, dl, nlast, nzv[p])) + bias;
+    if (threadIdx.x == 0 && p < np) {
+        const T kl = kval(kf, dl, nlast, nzv[p]);
+        for (int c = 0; c < nc; ++c) {
+            T s = 0;
+            for (int64_t b = 0; b < nblk; ++b) s += partial[(c * nblk + b) * 64 + p];
+            out[c * ldo + p] = (s + am[c] * kl) + bias[c];
+        }
     }
 }
 
@@ -263,16 +291,28 @@ void engine<T>::update_w(const T *alpha_host, T *w_host) {
     }
 }
 
-// One class through the paths that do not batch classes: linear (w . z), dense poly / rbf on rocBLAS + epilogue
-// (PLSSVM_MI_PRED_GEMM), sparse data through the kernel expansion or the brute-force kernel. Arguments are
-// validated by predict_multi. Sets predict_algo.
+// nclass models through the linear w path and the sparse paths (kernel expansion or brute force): the points are
+// prepared and uploaded once, and every pass over the support vectors serves up to KP_MULTI_W classes. Dense poly /
+// rbf on rocBLAS + epilogue (PLSSVM_MI_PRED_GEMM) is the one-class baseline: predict_multi calls it per class.
+// Arguments are validated by predict_multi. Sets predict_algo.
 template <typename T>
-void engine<T>::predict_one(const T *alpha_host, T bias, const T *Z, const int64_t *zrowptr, const int32_t *zcol,
-                            const void *zval, int zfmt, int64_t np, T *out) {
+void engine<T>::predict_shared(const T *alpha_host, int64_t nclass, int64_t lda, const T *bias, const T *Z,
+                               const int64_t *zrowptr, const int32_t *zcol, const void *zval, int zfmt, int64_t np, T *out,
+                               int64_t ldo) {
     MI_HIP_CHECK(hipSetDevice(device));
-    dev_buf<T> a;
-    a.alloc(std::max<int64_t>(n_pad, n), stream);
-    MI_HIP_CHECK(hipMemcpyAsync(a.get(), alpha_host, sizeof(T) * (size_t) n, hipMemcpyHostToDevice, stream));
+    ++predict_uploads;
+    // the model: A[nclass][ldd]; the classes' alpha[m], then their biases
+    const int64_t ldd = std::max<int64_t>(n_pad, n);
+    dev_buf<T> a, ab;
+    a.alloc(nclass * ldd, stream);
+    std::vector<T> abh((size_t) (2 * nclass));
+    for (int64_t c = 0; c < nclass; ++c) {
+        MI_HIP_CHECK(hipMemcpyAsync(a.get() + c * ldd, alpha_host + c * lda, sizeof(T) * (size_t) n, hipMemcpyHostToDevice, stream));
+        abh[(size_t) c] = alpha_host[c * lda + m];
+        abh[(size_t) (nclass + c)] = bias[c];
+    }
+    ab.alloc(2 * nclass, stream, false);
+    MI_HIP_CHECK(hipMemcpyAsync(ab.get(), abh.data(), sizeof(T) * (size_t) (2 * nclass), hipMemcpyHostToDevice, stream));
     // host densification of point p into dst (row-major, stride 1) — CSR input
     auto zget = [&](int64_t p, T *dst, int64_t stride) {
         if (Z) {
@@ -289,22 +329,29 @@ void engine<T>::predict_one(const T *alpha_host, T bias, const T *Z, const int64
     T nlast = 0;
     for (int64_t k = 0; k < d; ++k) nlast = std::fma(xlast_h[k], xlast_h[k], nlast);
 
-    if (kernel == 0) {  // w . z + bias
+    if (kernel == 0) {  // w_c . z + bias_c: W[nclass][d] by update_w_device per class, one launch per chunk of points
         predict_algo = PLSSVM_MI_PREDICT_LINEAR;
-        update_w_device(a.get());
+        predict_classes_per_pass = std::min<int64_t>(nclass, KP_MULTI_W);
+        dev_buf<T> W;
+        W.alloc(nclass * std::max<int64_t>(d, 1), stream, false);
+        for (int64_t c = 0; c < nclass; ++c) {
+            update_w_device(a.get() + c * ldd);
+            if (d > 0) MI_HIP_CHECK(hipMemcpyAsync(W.get() + c * d, w.get(), sizeof(T) * (size_t) d, hipMemcpyDeviceToDevice, stream));
+        }
         const int64_t pc = std::max<int64_t>(1, std::min<int64_t>(np, (int64_t) (256 << 20) / (int64_t) (sizeof(T) * std::max<int64_t>(d, 1))));
         std::vector<T> zh((size_t) (pc * d));
         dev_buf<T> zd, od;
         zd.alloc(pc * d, stream, false);
-        od.alloc(pc, stream, false);
+        od.alloc(nclass * pc, stream, false);
         for (int64_t p0 = 0; p0 < np; p0 += pc) {
             const int64_t c = std::min(pc, np - p0);
             for (int64_t p = 0; p < c; ++p) zget(p0 + p, zh.data() + p * d, 1);
             MI_HIP_CHECK(hipMemcpyAsync(zd.get(), zh.data(), sizeof(T) * (size_t) (c * d), hipMemcpyHostToDevice, stream));
-            hipLaunchKernelGGL(predict_linear_kernel<T>, dim3((unsigned) c), dim3(256), 0, stream, w.get(), zd.get(), d, bias,
-                               od.get());
+            hipLaunchKernelGGL(predict_linear_kernel<T>, dim3((unsigned) c), dim3(256), 0, stream, W.get(), zd.get(), d,
+                               ab.get() + nclass, nclass, od.get(), pc);
             MI_LAUNCH_CHECK();
-            MI_HIP_CHECK(hipMemcpyAsync(out + p0, od.get(), sizeof(T) * (size_t) c, hipMemcpyDeviceToHost, stream));
+            for (int64_t k = 0; k < nclass; ++k)
+                MI_HIP_CHECK(hipMemcpyAsync(out + k * ldo + p0, od.get() + k * pc, sizeof(T) * (size_t) c, hipMemcpyDeviceToHost, stream));
             MI_HIP_CHECK(hipStreamSynchronize(stream));
         }
         return;
@@ -313,7 +360,9 @@ void engine<T>::predict_one(const T *alpha_host, T bias, const T *Z, const int64
     if (!sparse) {
         // G = X_m Z^T on rocBLAS (column-major views: XT is (n_pad x d) with ld n_pad, a row-major
         // chunk of points is (d x c) with ld d), then the kernel-function / alpha epilogue
+        if (nclass != 1) throw mi_error(-6, "the rocBLAS predict baseline takes one class per call");
         predict_algo = PLSSVM_MI_PREDICT_GEMM;
+        predict_classes_per_pass = 1;
         if (blas == nullptr) MI_BLAS_CHECK(rocblas_create_handle(&blas));
         MI_BLAS_CHECK(rocblas_set_stream(blas, stream));
         const int64_t ldg = std::max<int64_t>(m, 1);
@@ -332,7 +381,7 @@ void engine<T>::predict_one(const T *alpha_host, T bias, const T *Z, const int64
             if (m > 0) MI_BLAS_CHECK(gemm_nn<T>(blas, m, c, d, XT.get(), n_pad, zd.get(), d, gd.get(), ldg));
             hipLaunchKernelGGL(predict_dense_epilogue_kernel<T>, dim3((unsigned) c), dim3(256), 0, stream, kf(), gd.get(),
                                ldg, m, kernel == 2 ? norms.get() : nullptr, a.get(), zd.get(), d, xlast.get(), nlast,
-                               bias, od.get());
+                               bias[0], od.get());
             MI_LAUNCH_CHECK();
             MI_HIP_CHECK(hipMemcpyAsync(out + p0, od.get(), sizeof(T) * (size_t) c, hipMemcpyDeviceToHost, stream));
             MI_HIP_CHECK(hipStreamSynchronize(stream));
@@ -395,42 +444,51 @@ void engine<T>::predict_one(const T *alpha_host, T bias, const T *Z, const int64
         MI_HIP_CHECK(hipMemcpyAsync(zcd.get(), zc.data(), sizeof(int32_t) * (size_t) znnz, hipMemcpyHostToDevice, stream));
         MI_HIP_CHECK(hipMemcpyAsync(zvd.get(), zv.data(), sizeof(T) * (size_t) znnz, hipMemcpyHostToDevice, stream));
     }
+    const int ncp = (int) std::min<int64_t>(nclass, KP_MULTI_W);  // classes per pass
+    predict_classes_per_pass = ncp;
+    dev_buf<T> oall;  // [nclass][np]
+    oall.alloc(nclass * np, stream, false);
+    auto download = [&] {
+        for (int64_t k = 0; k < nclass; ++k)
+            MI_HIP_CHECK(hipMemcpyAsync(out + k * ldo, oall.get() + k * np, sizeof(T) * (size_t) np, hipMemcpyDeviceToHost, stream));
+        MI_HIP_CHECK(hipStreamSynchronize(stream));
+    };
     if (kernel != 0 && csr.ex.on) {  // sparse poly / rbf model: through the kernel expansion (expand.hip)
-        dev_buf<T> oall;
-        oall.alloc(np, stream, false);
-        if (expansion_predict(a.get(), alpha_host[m], bias, zrd.get(), zcd.get(), zvd.get(), np, max_nnz_z, zabs_max,
-                              znorm_max, nlast, oall.get())) {
+        if (expansion_predict(a.get(), ldd, nclass, ab.get(), zrd.get(), zcd.get(), zvd.get(), np, max_nnz_z, zabs_max,
+                              znorm_max, nlast, oall.get(), np)) {
             predict_algo = PLSSVM_MI_PREDICT_EXPANSION;
-            MI_HIP_CHECK(hipMemcpyAsync(out, oall.get(), sizeof(T) * (size_t) np, hipMemcpyDeviceToHost, stream));
-            MI_HIP_CHECK(hipStreamSynchronize(stream));
+            download();
             return;
         }
     }
     predict_algo = PLSSVM_MI_PREDICT_BRUTE;
-    const int64_t nblk = std::max<int64_t>(1, ceil_div(m, PRED_ROWS));
-    dev_buf<T> ztd, nzd, pd, od;
+    const int64_t nblk = m > 0 ? ceil_div(m, PRED_ROWS) : (int64_t) 0;
+    dev_buf<T> ztd, nzd, pd;
     ztd.alloc(d * 64, stream, false);
     nzd.alloc(64, stream, false);
-    pd.alloc(nblk * 64, stream);
-    od.alloc(64, stream, false);
+    pd.alloc(std::max<int64_t>(1, ncp * nblk * 64), stream);
     for (int64_t p0 = 0; p0 < np; p0 += 64) {
         const int64_t c = std::min<int64_t>(64, np - p0);
         MI_HIP_CHECK(hipMemsetAsync(ztd.get(), 0, sizeof(T) * (size_t) (d * 64), stream));
         hipLaunchKernelGGL(zt_scatter_kernel<T>, dim3(1), dim3(64), 0, stream, zrd.get(), zcd.get(), zvd.get(), p0, c,
                            ztd.get(), nzd.get());
         MI_LAUNCH_CHECK();
-        if (m > 0)
-            hipLaunchKernelGGL(predict_csr_kernel<T>, dim3((unsigned) ceil_div(m, PRED_ROWS)), dim3(256), 0, stream, kf(),
-                               csr.rowptr.get(), csr.col.get(), csr.val.get(), m, ztd.get(), nzd.get(), norms.get(),
-                               a.get(), pd.get());
-        MI_LAUNCH_CHECK();
-        hipLaunchKernelGGL(predict_csr_final_kernel<T>, dim3(64), dim3(256), 0, stream, kf(), pd.get(),
-                           m > 0 ? ceil_div(m, PRED_ROWS) : (int64_t) 0, ztd.get(), nzd.get(), d, xlast.get(), nlast,
-                           a.get(), m, bias, c, od.get());
-        MI_LAUNCH_CHECK();
-        MI_HIP_CHECK(hipMemcpyAsync(out + p0, od.get(), sizeof(T) * (size_t) c, hipMemcpyDeviceToHost, stream));
-        MI_HIP_CHECK(hipStreamSynchronize(stream));
+        for (int64_t c0 = 0; c0 < nclass; c0 += ncp) {
+            const int nc = (int) std::min<int64_t>(ncp, nclass - c0);
+            if (m > 0) {
+                auto csr_kernel = nc == 1 ? predict_csr_kernel<T, 1> : predict_csr_kernel<T, KP_MULTI_W>;
+                hipLaunchKernelGGL(csr_kernel, dim3((unsigned) nblk), dim3(256), 0, stream, kf(), csr.rowptr.get(),
+                                   csr.col.get(), csr.val.get(), m, ztd.get(), nzd.get(), norms.get(), a.get() + c0 * ldd,
+                                   ldd, nc, pd.get());
+                MI_LAUNCH_CHECK();
+            }
+            hipLaunchKernelGGL(predict_csr_final_kernel<T>, dim3(64), dim3(256), 0, stream, kf(), pd.get(), nblk, ztd.get(),
+                               nzd.get(), d, xlast.get(), nlast, ab.get() + c0, ab.get() + nclass + c0, nc, c,
+                               oall.get() + c0 * np + p0, np);
+            MI_LAUNCH_CHECK();
+        }
     }
+    download();
 }
 
 // Dense data, poly / rbf: all classes per pass over the kernel values (predict_tiles.hip). The points go up in chunks,
@@ -443,6 +501,8 @@ void engine<T>::predict_tiles(const T *alpha_host, int64_t nclass, int64_t lda, 
     MI_HIP_CHECK(hipSetDevice(device));
     predict_algo = PLSSVM_MI_PREDICT_TILES;
     const int ncp = (int) std::min<int64_t>(nclass, KP_MULTI_W);  // classes per pass
+    predict_classes_per_pass = ncp;
+    predict_uploads = 1;
     const int64_t nseg = predict_segments(nb);
     // the model: A[nclass][n_pad], zero from row m on; the classes' alpha[m], then their biases
     dev_buf<T> A, ab;
@@ -513,9 +573,10 @@ void engine<T>::predict_tiles(const T *alpha_host, int64_t nclass, int64_t lda, 
 // gpu_csvm::predict (src/plssvm/backends/gpu_csvm.cpp:52-120) for nclass models on the same support vectors:
 // alpha_host[nclass][lda] and bias[nclass] (host), out[nclass][ldo] (host). Points: dense row-major Z[np][dz] or CSR
 // (zrowptr, zcol, zval in zfmt). Dense data with the polynomial / rbf kernel: the fused tile kernel, all classes per
-// pass (PLSSVM_MI_PRED_GEMM=1, read per call: rocBLAS + epilogue, once per class). Everything else — the linear w
-// path, sparse data — runs the classes one after another through predict_one. Row c is bitwise the nclass = 1 call
-// with (alpha_c, bias_c).
+// pass (PLSSVM_MI_PRED_GEMM=1, read per call: rocBLAS + epilogue, once per class). The linear w path and sparse data:
+// predict_shared, the points prepared once and up to KP_MULTI_W classes per pass over the support vectors
+// (PLSSVM_MI_PRED_SEQ=1, read per call: the classes one after another, each with its own point preparation). Row c is
+// bitwise the nclass = 1 call with (alpha_c, bias_c).
 template <typename T>
 void engine<T>::predict_multi(const T *alpha_host, int64_t nclass, int64_t lda, const T *bias, const T *Z,
                               const int64_t *zrowptr, const int32_t *zcol, const void *zval, int zfmt, int64_t np,
@@ -535,12 +596,19 @@ void engine<T>::predict_multi(const T *alpha_host, int64_t nclass, int64_t lda, 
     if (lda < n || ldo < np) throw mi_error(-1, "leading dimension too small");
     const char *ge = std::getenv("PLSSVM_MI_PRED_GEMM");
     const bool gemm = ge != nullptr && std::strcmp(ge, "0") != 0;
+    predict_uploads = 0;
     if (!sparse && kernel != 0 && !gemm) {
         predict_tiles(alpha_host, nclass, lda, bias, Z, zrowptr, zcol, zval, zfmt, np, out, ldo);
         return;
     }
+    const char *se = std::getenv("PLSSVM_MI_PRED_SEQ");
+    const bool seq = (se != nullptr && std::strcmp(se, "0") != 0) || (!sparse && kernel != 0);
+    if (!seq) {
+        predict_shared(alpha_host, nclass, lda, bias, Z, zrowptr, zcol, zval, zfmt, np, out, ldo);
+        return;
+    }
     for (int64_t c = 0; c < nclass; ++c)
-        predict_one(alpha_host + c * lda, bias[c], Z, zrowptr, zcol, zval, zfmt, np, out + c * ldo);
+        predict_shared(alpha_host + c * lda, 1, lda, bias + c, Z, zrowptr, zcol, zval, zfmt, np, out + c * ldo, ldo);
 }
 
 template <typename T>

@@ -185,8 +185,119 @@ class csvm : public csvm_interface<T> {
         this->QA_cost_ = qa;
     }
 
-    // csvm<T>::write_model (src/plssvm/csvm.cpp:60-204): positive-label support vectors first
+    // ---- one-vs-all models of K >= 2 classes (build-defined; the reference, v1.2.0, is binary only) ----
+    // learn_multi: the classes are the distinct values of the parameter set's class_labels, ascending; per class
+    // exactly learn() on +1 (the point is of the class) / -1, all classes in one plssvm_mi_learn_multi call on every rank
+    void learn_multi() { learn_multi(this->num_features_); }
+    void learn_multi(std::size_t imax) {
+        const auto &p = this->params_;
+        if (p.class_labels.empty()) throw exception{ "No labels given for training! Maybe the data is only usable for prediction?" };
+        if (p.class_labels.size() != this->num_data_points_)
+            throw exception{ "Number of labels (" + std::to_string(p.class_labels.size()) +
+                             ") must match the number of data points (" + std::to_string(this->num_data_points_) + ")!" };
+        std::vector<T> cls = p.class_labels;
+        std::sort(cls.begin(), cls.end());
+        cls.erase(std::unique(cls.begin(), cls.end()), cls.end());
+        if (cls.size() < 2) throw exception{ "learn_multi needs at least 2 classes" };
+        const size_t K = cls.size(), n = this->num_data_points_;
+        std::vector<T> Y(K * n);
+        for (size_t c = 0; c < K; ++c)
+            for (size_t i = 0; i < n; ++i) Y[c * n + i] = p.class_labels[i] == cls[c] ? T(1) : T(-1);
+        if (!on_device_) setup_data_on_device();
+        const size_t R = (size_t) grp_->size();
+        std::vector<std::vector<T>> al(R, std::vector<T>(K * n));
+        std::vector<std::vector<double>> bi(R, std::vector<double>(K)), tr(R, std::vector<double>(K * (imax + 1), 0.0));
+        std::vector<std::vector<int64_t>> its(R, std::vector<int64_t>(K, 0));
+        on_all([&](int r, plssvm_mi_ctx *c) {
+            return plssvm_mi_learn_multi(c, Y.data(), (int64_t) K, (int64_t) n, (int64_t) imax, (double) this->epsilon_,
+                                         al[(size_t) r].data(), bi[(size_t) r].data(), tr[(size_t) r].data(),
+                                         its[(size_t) r].data());
+        });
+        classes_ = std::move(cls);
+        alphas_ = std::move(al[0]);
+        biases_.assign(bi[0].begin(), bi[0].end());
+        iterations_multi_ = std::move(its[0]);
+        traces_.clear();
+        for (size_t c = 0; c < K; ++c)
+            traces_.emplace_back(tr[0].begin() + c * (imax + 1), tr[0].begin() + c * (imax + 1) + iterations_multi_[c] + 1);
+    }
+    // the model of a one-vs-all model file: classes [K], alphas [K][n] (row-major), rhos [K]
+    void set_model_multi(std::vector<T> classes, std::vector<T> alphas, const std::vector<T> &rhos) {
+        if (classes.empty() || rhos.size() != classes.size() || alphas.size() != classes.size() * this->num_data_points_)
+            throw exception{ "Number of weights (" + std::to_string(alphas.size()) + ") must match the number of classes (" +
+                             std::to_string(classes.size()) + ") times the number of data points (" +
+                             std::to_string(this->num_data_points_) + ")!" };
+        classes_ = std::move(classes);
+        alphas_ = std::move(alphas);
+        biases_.clear();
+        for (const T r : rhos) biases_.push_back(-r);
+    }
+    // decision values [K][np] (row-major) of the points held by `points` (dense or CSR): every class in one call
+    std::vector<T> predict_values_multi(const parameter<T> &points) {
+        if (classes_.empty()) throw exception{ "No alphas provided for prediction!" };
+        if (!on_device_) setup_data_on_device();
+        const int64_t K = (int64_t) classes_.size(), np = points.num_data_points, n = (int64_t) this->num_data_points_;
+        const size_t len = (size_t) (K * std::max<int64_t>(np, 1));
+        std::vector<T> out(len);
+        auto sc = scratch(len);
+        const std::vector<double> b(biases_.begin(), biases_.end());
+        on_all([&](int r, plssvm_mi_ctx *c) {
+            T *o = r == 0 ? out.data() : sc[(size_t) r].data();
+            if (points.sparse)
+                return plssvm_mi_predict_multi_csr(c, alphas_.data(), K, n, b.data(), points.rowptr.data(), points.col.data(),
+                                                   points.val.data(), PLSSVM_MI_VAL_REAL, np, points.num_features, o,
+                                                   std::max<int64_t>(np, 1));
+            return plssvm_mi_predict_multi_dense(c, alphas_.data(), K, n, b.data(), points.dense.data(), np,
+                                                 points.num_features, o, std::max<int64_t>(np, 1));
+        });
+        return out;
+    }
+    // the class with the largest decision value, the lowest class index on a tie
+    std::vector<T> predict_label_multi(const parameter<T> &points) {
+        const std::vector<T> v = predict_values_multi(points);
+        const size_t K = classes_.size(), np = (size_t) points.num_data_points;
+        std::vector<T> l(np);
+        for (size_t p = 0; p < np; ++p) {
+            size_t best = 0;
+            for (size_t c = 1; c < K; ++c)
+                if (v[c * np + p] > v[best * np + p]) best = c;
+            l[p] = classes_[best];
+        }
+        return l;
+    }
+    // fraction of the points whose predicted label equals points.class_labels
+    T accuracy_multi(const parameter<T> &points) {
+        if (points.class_labels.empty()) throw exception{ "No labels given for the accuracy calculation!" };
+        const std::vector<T> l = predict_label_multi(points);
+        if (l.size() != points.class_labels.size())
+            throw exception{ "Number of data points to predict and correct labels mismatch!" };
+        std::size_t ok = 0;
+        for (std::size_t i = 0; i < l.size(); ++i) ok += l[i] == points.class_labels[i];
+        return (T) ok / (T) l.size();
+    }
+    const std::vector<T> &classes() const { return classes_; }
+    const std::vector<T> &alphas() const { return alphas_; }  // [K][n], row-major
+    const std::vector<T> &biases() const { return biases_; }
+    const std::vector<int64_t> &iterations_multi() const { return iterations_multi_; }
+    const std::vector<std::vector<double>> &residual_traces() const { return traces_; }
+
+    // csvm<T>::write_model (src/plssvm/csvm.cpp:60-204): positive-label support vectors first. After learn_multi /
+    // set_model_multi with three or more classes: the one-vs-all layout (parameter<T>::model_text_multi); two classes
+    // are a binary model and are written by learn()
     void write_model(const std::string &filename) const {
+        if (classes_.size() >= 3) {
+            const auto &p = this->params_;
+            if (p.class_labels.size() != this->num_data_points_)
+                throw exception{ "No class labels given! A one-vs-all model file needs the class of every support vector." };
+            std::vector<int64_t> pc(p.class_labels.size());
+            for (size_t i = 0; i < pc.size(); ++i)
+                pc[i] = (int64_t) (std::lower_bound(classes_.begin(), classes_.end(), p.class_labels[i]) - classes_.begin());
+            std::vector<std::vector<T>> al;
+            for (size_t c = 0; c < classes_.size(); ++c)
+                al.emplace_back(alphas_.begin() + c * this->num_data_points_, alphas_.begin() + (c + 1) * this->num_data_points_);
+            write_text(filename, p.model_text_multi(classes_, pc, al, biases_));
+            return;
+        }
         if (this->alpha_ptr_ == nullptr) throw exception{ "No alphas given! Maybe a call to 'learn()' is missing?" };
         const auto &p = this->params_;
         const auto &alpha_ = *this->alpha_ptr_;
@@ -222,10 +333,7 @@ class csvm : public csvm_interface<T> {
                 out += "\n";
             }
         }
-        std::FILE *fp = std::fopen(filename.c_str(), "w");
-        if (!fp) throw std::runtime_error("Can't open model file '" + filename + "'!");
-        std::fwrite(out.data(), 1, out.size(), fp);
-        std::fclose(fp);
+        write_text(filename, out);
     }
 
     // model use (csvm.hpp:123-178; gpu_csvm::update_w / predict, gpu_csvm.cpp:52-127,327-350). Without a
@@ -282,13 +390,15 @@ class csvm : public csvm_interface<T> {
     int64_t iterations() const { return iterations_; }
     const std::vector<double> &residual_trace() const { return trace_; }
 
-    static std::string shortest(T v) {  // fmt "{}" of a floating point value: shortest round-trip form
-        char buf[64];
-        const auto r = std::to_chars(buf, buf + sizeof buf, v);
-        return std::string(buf, r.ptr);
-    }
+    static std::string shortest(T v) { return plssvm::mi355x::shortest(v); }  // fmt "{}": shortest round-trip form
 
   private:
+    static void write_text(const std::string &filename, const std::string &out) {
+        std::FILE *fp = std::fopen(filename.c_str(), "w");
+        if (!fp) throw std::runtime_error("Can't open model file '" + filename + "'!");
+        std::fwrite(out.data(), 1, out.size(), fp);
+        std::fclose(fp);
+    }
     struct progress_state {
         int64_t imax;
         double target, ms_total;
@@ -330,6 +440,10 @@ class csvm : public csvm_interface<T> {
     std::vector<double> trace_;
     int64_t iterations_ = 0;
     bool on_device_ = false;
+    // the one-vs-all model (learn_multi / set_model_multi)
+    std::vector<T> classes_, alphas_, biases_;
+    std::vector<int64_t> iterations_multi_;
+    std::vector<std::vector<double>> traces_;
 };
 
 }  // namespace plssvm::mi355x

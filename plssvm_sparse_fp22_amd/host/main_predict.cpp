@@ -3,7 +3,9 @@
 // plssvm::mi355x::csvm<T> (host/csvm.hpp) on libplssvm_mi355x.so.
 //
 // Additions (not in the reference): --sparse keeps model and test data as CSR (the reference
-// densifies), --single predicts in fp32, --device picks the GPU.
+// densifies), --single predicts in fp32, --device picks the GPU. A model file with nr_class >= 3 (plssvm-train
+// --multiclass) selects the one-vs-all route: the label of the class with the largest decision value per line, and the
+// accuracy as exact label equality.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -52,9 +54,10 @@ int predict(const cli &c) {
     parameter<T> model, test;
     model.input_filename = c.pos[0];
     const std::string predict_filename = c.pos.size() > 2 ? c.pos[2] : model.predict_name_from_input();
-    test.parse_test_file(c.pos[0], sparse);
+    test.parse_test_file(c.pos[0], sparse, 0, true);
     model.parse_model_file(c.pos[1], sparse, test.num_features);
-    if (test.num_features < model.num_features) test.parse_test_file(c.pos[0], sparse, model.num_features);
+    if (test.num_features < model.num_features) test.parse_test_file(c.pos[0], sparse, model.num_features, true);
+    const bool multi = model.nr_class >= 3;
     if (print_info) {
         std::printf("\ntask: prediction\nkernel type: %s -> ", kernel_name(model.kernel));
         switch (model.kernel) {
@@ -65,13 +68,26 @@ int predict(const cli &c) {
                 break;
             default: std::printf("exp(-gamma*|u-v|^2)\ngamma: %s\n", csvm<T>::shortest(model.gamma).c_str()); break;
         }
+        std::string rho = csvm<T>::shortest(model.rho);
+        if (multi) {
+            rho.clear();
+            for (const T r : model.rhos) rho += (rho.empty() ? "" : " ") + csvm<T>::shortest(r);
+        }
         std::printf("rho: %s\ninput file (data set): '%s'\ninput file (model): '%s'\noutput file (prediction): '%s'\n\n",
-                    csvm<T>::shortest(model.rho).c_str(), c.pos[0].c_str(), c.pos[1].c_str(), predict_filename.c_str());
+                    rho.c_str(), c.pos[0].c_str(), c.pos[1].c_str(), predict_filename.c_str());
     }
     const int device = c.opt.count("device") ? std::stoi(c.opt.at("device")) : 0;
     csvm<T> svm(model, device);
-    svm.set_model(model.alpha, model.rho);
-    const std::vector<T> labels = svm.predict_label(test);
+    std::vector<T> labels;
+    if (multi) {
+        std::vector<T> flat;
+        for (const auto &a : model.alphas) flat.insert(flat.end(), a.begin(), a.end());
+        svm.set_model_multi(model.classes, std::move(flat), model.rhos);
+        labels = svm.predict_label_multi(test);
+    } else {
+        svm.set_model(model.alpha, model.rho);
+        labels = svm.predict_label(test);
+    }
 
     const auto t0 = std::chrono::steady_clock::now();
     {
@@ -86,7 +102,8 @@ int predict(const cli &c) {
                     (long long) std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count());
     if (!test.labels.empty()) {
         std::size_t correct = 0;
-        for (std::size_t i = 0; i < labels.size(); ++i) correct += test.labels[i] * labels[i] > T(0);
+        for (std::size_t i = 0; i < labels.size(); ++i)
+            correct += multi ? test.class_labels[i] == labels[i] : test.labels[i] * labels[i] > T(0);
         std::printf("Accuracy = %s%% (%zu/%zu) (classification)\n",
                     csvm<T>::shortest((T) correct / (T) labels.size() * T(100)).c_str(), correct, labels.size());
     }

@@ -4,7 +4,8 @@
 //
 // Additions (not in the reference): --sparse keeps LIBSVM input as CSR (the reference densifies),
 // --max_iter overrides the CG limit (default: num_features, csvm.cpp:256), --single trains in fp32
-// (the reference selects that at compile time, main_train.cpp:21-25), --device picks the GPU.
+// (the reference selects that at compile time, main_train.cpp:21-25), --device picks the GPU, --multiclass trains
+// one-vs-all over the file's distinct labels (three or more) and writes the one-vs-all model file.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -42,7 +43,8 @@ const char *kHelp =
     "      --single               train in single precision (float)\n"
     "      --device arg           train on this one HIP device (default: every visible device)\n"
     "      --devices arg          comma-separated device list, one rank per entry (a device listed twice:\n"
-    "                             in-process host exchange instead of RCCL)\n";
+    "                             in-process host exchange instead of RCCL)\n"
+    "      --multiclass           one-vs-all over the file's distinct labels (three or more classes)\n";
 
 template <typename T>
 int train(const cli &c) {
@@ -76,8 +78,19 @@ int train(const cli &c) {
     params.input_filename = c.pos[0];
     if (c.pos.size() > 1) params.model_filename = c.pos[1];
     const auto t0 = std::chrono::steady_clock::now();
-    params.parse_train_file(c.pos[0], c.opt.count("sparse") > 0);
+    const bool multiclass = c.opt.count("multiclass") > 0;
+    params.parse_train_file(c.pos[0], c.opt.count("sparse") > 0, multiclass);
     if (c.pos.size() > 1) params.model_filename = c.pos[1];
+    if (multiclass) {
+        std::vector<T> distinct = params.class_labels;
+        std::sort(distinct.begin(), distinct.end());
+        distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+        if (distinct.size() < 3) {
+            std::fprintf(stderr, "--multiclass needs at least 3 distinct labels, but %zu were given! Train without it for two classes.\n",
+                         distinct.size());
+            return EXIT_FAILURE;
+        }
+    }
     if (params.print_info) {
         std::printf("Read %lld data points with %lld features in %lldms using the libsvm parser from file '%s'.\n\n",
                     (long long) params.num_data_points, (long long) params.num_features,
@@ -120,8 +133,24 @@ int train(const cli &c) {
     }
     // learn() prints the reference's setup line, one line per CG iteration and the solve summary
     // (csvm.cpp:226-266, OpenMP/csvm.cpp:115-117,161-166)
-    if (c.opt.count("max_iter")) svm.learn((std::size_t) std::stoll(c.opt.at("max_iter")));
-    else svm.learn();
+    if (multiclass) {
+        // one summary line per class instead of the per-iteration lines (the multi entry points report no progress)
+        if (c.opt.count("max_iter")) svm.learn_multi((std::size_t) std::stoll(c.opt.at("max_iter")));
+        else svm.learn_multi();
+        if (params.print_info) {
+            for (size_t k = 0; k < svm.classes().size(); ++k) {
+                const std::vector<double> &tr = svm.residual_traces()[k];
+                std::printf("Class %s: finished after %lld iterations with a residuum of %s (target: %s).\n",
+                            csvm<T>::shortest(svm.classes()[k]).c_str(), (long long) svm.iterations_multi()[k],
+                            csvm<T>::shortest((T) tr.back()).c_str(),
+                            csvm<T>::shortest(params.epsilon * params.epsilon * (T) tr.front()).c_str());
+            }
+        }
+    } else if (c.opt.count("max_iter")) {
+        svm.learn((std::size_t) std::stoll(c.opt.at("max_iter")));
+    } else {
+        svm.learn();
+    }
     svm.write_model(params.model_filename);
     if (params.print_info) std::printf("Wrote model file ('%s').\n", params.model_filename.c_str());
     return EXIT_SUCCESS;
@@ -134,7 +163,7 @@ int main(int argc, char **argv) {
         const cli c = parse_cli(argc, argv, { { "t", "kernel_type" }, { "d", "degree" }, { "g", "gamma" }, { "r", "coef0" },
                                               { "c", "cost" }, { "e", "epsilon" }, { "b", "backend" },
                                               { "p", "target_platform" }, { "q", "quiet" }, { "h", "help" } },
-                                { "quiet", "help", "sparse", "single" });
+                                { "quiet", "help", "sparse", "single", "multiclass" });
         if (c.opt.count("help")) {
             std::printf("%s", kHelp);
             return EXIT_SUCCESS;

@@ -11,7 +11,11 @@
   through the kernel expansion (the model's column moments once, then per point its features' moment
   sums and the support vectors sharing two or more features with it), beside the brute-force kernel
   (every support vector entry gathered per 64 points, PLSSVM_MI_PRED_BRUTE);
-* linear update_w on config 3 (the SELL CSC pass, w = sum alpha_i x_i).
+* linear update_w on config 3 (the SELL CSC pass, w = sum alpha_i x_i);
+* --sparse-classes K[,K...] runs only the sparse rows, once per K, through predict_values_multi: config 3-RBF's model
+  through the expansion and through the brute-force sweep, and config 3's linear model (w_c . z). The points are
+  prepared once and up to 8 classes share each pass over the support vectors; PLSSVM_MI_PRED_SEQ=1 in the
+  environment runs the classes one after another (the A/B baseline of the shared pass).
 Times include the host transfers of the points and results (the C ABI takes host buffers); alpha is
 random (the model's alphas do not change the work). Prints one JSON line.
 """
@@ -40,11 +44,41 @@ def timed(fn, reps=3):
 ALGO = {v: k for k, v in vars(pm._abi).items() if k.startswith("PREDICT_") and k != "PREDICT_SEG_TILES"}
 
 
+def sparse_classes(res, rng, ks, reps):
+    """config 3-RBF's model (expansion, brute force) and config 3's linear model with K classes per call"""
+    n, d, k, npts = 1_000_000, 50_000, 50, 4096
+    csr, y = datagen.sparse_csr(n, d, k, seed=3, dtype=np.float32)
+    zc, _ = datagen.sparse_csr(npts, d, k, seed=11, dtype=np.float32)
+    A = rng.standard_normal((max(ks), n)).astype(np.float32)
+    b = rng.standard_normal(max(ks)).astype(np.float32)
+    seq = os.environ.get("PLSSVM_MI_PRED_SEQ", "0") != "0"
+    for kern, rows in (("rbf", (("csr_rbf_1m_expansion", False, reps), ("csr_rbf_1m_brute", True, 1))),
+                       ("linear", (("csr_linear_1m", False, 1),))):
+        p = pm.Parameter(kern, gamma=1.0 / d, real_type=np.float32)
+        p.csr, p.labels = csr, y
+        with pm.CSVM(p) as svm:
+            svm.setup_data_on_device()
+            for name, brute, r in rows:
+                if brute:
+                    os.environ["PLSSVM_MI_PRED_BRUTE"] = "1"
+                row = {"support_vectors": n, "d": d, "points": npts, "dtype": "f32", "reps": r, "sequential": seq}
+                for K in ks:
+                    s, _ = timed(lambda: svm.predict_values_multi(zc, alphas=A[:K], biases=b[:K]), r)
+                    row[f"K{K}"] = {"seconds": s, "seconds_per_class": s / K,
+                                    "predict_algo": ALGO[svm.info()["predict_algo"]]}
+                    if hasattr(svm, "predict_stats"):
+                        row[f"K{K}"]["predict_stats"] = svm.predict_stats()
+                os.environ.pop("PLSSVM_MI_PRED_BRUTE", None)
+                res[name] = row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--classes", default=None, metavar="K[,K...]",
                     help="only the dense row, with K one-vs-all classes per predict_values_multi call")
     ap.add_argument("--gemm", action="store_true", help="PLSSVM_MI_PRED_GEMM=1: rocBLAS + epilogue, once per class")
+    ap.add_argument("--sparse-classes", default=None, metavar="K[,K...]",
+                    help="only the sparse rows (expansion, brute force, linear), K classes per predict_values_multi call")
     ap.add_argument("--points", type=int, default=100_000, help="support vectors and predict points of the dense row")
     ap.add_argument("--reps", type=int, default=3)
     args = ap.parse_args()
@@ -52,6 +86,10 @@ def main():
         os.environ["PLSSVM_MI_PRED_GEMM"] = "1"
     res = {}
     rng = np.random.default_rng(7)
+    if args.sparse_classes is not None:
+        sparse_classes(res, rng, [int(v) for v in args.sparse_classes.split(",")], args.reps)
+        print(json.dumps(res), flush=True)
+        return
     # dense RBF (config 2 model)
     n, d, npts = args.points, 256, args.points
     X, y = datagen.blobs(n, d, seed=2)
