@@ -3036,8 +3036,10 @@ bool engine<T>::expansion_predict(const T *alpha_dev, int64_t lda, int64_t nclas
     if (!ex.on || kernel == 0 || m <= 0 || max_nnz_z > PRED_ZCAP) return false;
     if (std::getenv("PLSSVM_MI_PRED_BRUTE") != nullptr) return false;
     // the model's Taylor degree covers |2 g x z| up to umax; the factored rbf form |z|^2 in range
-    const double xabs = std::sqrt(ex.umax / std::max(2.0 * std::fabs((double) gamma), 1e-300));
-    if (kernel == 2 && 2.0 * std::fabs((double) gamma) * xabs * zabs_max > ex.umax) return false;
+    // (|2 g x z| <= umax = 2 |g| max x^2 for every x of the model iff max z^2 <= max x^2; formed like umax, so points
+    // whose largest |z| equals the model's largest |x| stay in range exactly — through sqrt(umax / 2 |g|) the
+    // comparison rounded either way there)
+    if (kernel == 2 && 2.0 * std::fabs((double) gamma) * (zabs_max * zabs_max) > ex.umax) return false;
     if (kernel == 2 && std::fabs((double) gamma) * znorm_max > (sizeof(T) == 8 ? 300.0 : 40.0)) return false;
     const phi_fn phi = make_phi<T>(kernel, degree, gamma, coef0);
     const int ncp = (int) std::min<int64_t>(nclass, KP_MULTI_W);  // classes per pass

@@ -363,9 +363,10 @@ __global__ __launch_bounds__((gram_wg<T, KERNEL>())) void gram_kp_kernel(const g
                                                        const int32_t *__restrict__ rowoff,
                                                        const uint16_t *__restrict__ pj, const T *__restrict__ ps,
                                                        const T *__restrict__ norms, const T *__restrict__ ev,
-                                                       const T *__restrict__ p, T *__restrict__ slab_row,
-                                                       T *__restrict__ slab_col, int64_t m, int64_t m_pad, kfun<T> kf,
-                                                       T kappa, const cg_scalars<T> *__restrict__ status) {
+                                                       const double *__restrict__ cbnd, const T *__restrict__ p,
+                                                       T *__restrict__ slab_row, T *__restrict__ slab_col, int64_t m,
+                                                       int64_t m_pad, kfun<T> kf, T kappa,
+                                                       const cg_scalars<T> *__restrict__ status) {
     constexpr int NT = gram_wg<T, KERNEL>();
     constexpr int CW = GRAM_CW, NWAVE = NT / 64;
     constexpr bool NEED_N = KERNEL == 2, NEED_E = KERNEL == 2;
@@ -375,7 +376,7 @@ __global__ __launch_bounds__((gram_wg<T, KERNEL>())) void gram_kp_kernel(const g
     __shared__ acc_t colacc[CW];
     __shared__ acc_t rowacc[GRAM_RB];
     __shared__ int32_t ro[GRAM_RB + 1];
-    __shared__ T wmax[NWAVE];
+    __shared__ double wmax[NWAVE];
     if (status != nullptr && status->converged) return;
     const gram_cell cell = cells[xcd_remap(blockIdx.x, gridDim.x)];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -383,19 +384,22 @@ __global__ __launch_bounds__((gram_wg<T, KERNEL>())) void gram_kp_kernel(const g
     const int rows = (int) min<int64_t>(GRAM_RB, m - I0);
     const int wlen = (int) min<int64_t>(CW, m - W0);
     const T gamma = kf.gamma;
-    T pmax = 0;
+    // bound on the cell's terms c_ij p_j and c_ij p_i: cbnd[t] bounds |c| over the pairs of row t (setup, from the
+    // largest |s| the row meets), so a vector that lives on rows of small |c| keeps its digits (a bound from the
+    // cell's largest |s| alone is (smax / s)^degree too coarse for them: the polynomial kernel of degree 16)
+    double pmax = 0;
     for (int t = tid; t < CW; t += NT) {
         const bool ok = t < wlen;
         if (NEED_N) wn[t] = ok ? norms[W0 + t] : T(0);
         if (NEED_E) we[t] = ok ? ev[W0 + t] : T(0);
         const T pv = ok ? (FACT ? ev[W0 + t] * p[W0 + t] : p[W0 + t]) : T(0);
         wp[t] = pv;
-        pmax = max(pmax, fabs(pv));
+        if (ok) pmax = max(pmax, fabs((double) pv) * cbnd[W0 + t]);
         colacc[t] = 0;
     }
     for (int t = tid; t < GRAM_RB; t += NT) {
         rowacc[t] = 0;
-        if (t < rows) pmax = max(pmax, fabs(FACT ? ev[I0 + t] * p[I0 + t] : p[I0 + t]));
+        if (t < rows) pmax = max(pmax, fabs((double) (FACT ? ev[I0 + t] * p[I0 + t] : p[I0 + t])) * cbnd[I0 + t]);
     }
     for (int t = tid; t <= rows; t += NT) ro[t] = rowoff[cell.rowoff + t];
 #pragma unroll
@@ -405,23 +409,9 @@ __global__ __launch_bounds__((gram_wg<T, KERNEL>())) void gram_kp_kernel(const g
     pmax = wmax[0];
 #pragma unroll
     for (int w = 1; w < NWAVE; ++w) pmax = max(pmax, wmax[w]);
-    // bound on |c| (|g| for the factored rbf) over the cell's pairs
-    double cb;
-    if (FACT) {
-        cb = expm1(2.0 * fabs((double) gamma) * cell.smax);
-    } else if (KERNEL == 2) {
-        cb = 1.0;
-    } else if (KERNEL == 1) {
-        const double bse = fabs((double) gamma) * cell.smax + fabs((double) kf.coef0);
-        double a = 1.0, b = 1.0;
-        for (int q = 0; q < kf.degree; ++q) a *= bse, b *= fabs((double) kf.coef0);
-        cb = a + b;
-    } else {
-        cb = cell.smax;
-    }
     // quantum 2^qe, clamped to the smallest normal of T (terms below it are denormal anyway)
     constexpr int emin = sizeof(T) == 8 ? -1022 : -126;
-    const double bound = cb * (double) pmax * 1.0000001;
+    const double bound = pmax * 1.0000001;
     const int qe = bound > 0.0 && isfinite(bound) ? max(emin, ilogb(bound) + 1 - 50) : emin;
     const double inv_q = ldexp(1.0, -qe);
     // one pair's term (|x| < 2^50): magic-add rounding; row partials (up to 512 terms): full conversion
@@ -567,7 +557,8 @@ __global__ __launch_bounds__((gram_wg<T, KERNEL>())) void gram_kp_kernel(const g
     }
 }
 
-// per cell: max |s| over its pairs (the fixed-point bound of the K·p kernel)
+// per cell: max |s| over its pairs (setup's choice of the rbf pair form; the K·p kernel's fixed-point bound is per
+// row, gram_row_smax_kernel below)
 template <typename T>
 __global__ __launch_bounds__(256) void gram_cell_smax_kernel(gram_cell *__restrict__ cells,
                                                              const int64_t *__restrict__ rb_base,
@@ -585,6 +576,67 @@ __global__ __launch_bounds__(256) void gram_cell_smax_kernel(gram_cell *__restri
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) cell.smax = (double) max(max(part[0], part[1]), max(part[2], part[3]));
+}
+
+// per row: max |s| over the pairs it takes part in, as the row or as the partner. One workgroup per cell, the
+// partners' maxima in LDS first. rs holds non-negative doubles, whose bit patterns order like the values.
+template <typename T>
+__global__ __launch_bounds__(256) void gram_row_smax_kernel(const gram_cell *__restrict__ cells,
+                                                            const int64_t *__restrict__ rb_base,
+                                                            const int32_t *__restrict__ rowoff,
+                                                            const uint16_t *__restrict__ pj, const T *__restrict__ ps,
+                                                            int64_t m, unsigned long long *__restrict__ rs) {
+    __shared__ unsigned long long cmax[GRAM_CW];
+    const gram_cell cell = cells[blockIdx.x];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t I0 = (int64_t) cell.I * GRAM_RB, W0 = (int64_t) cell.W * GRAM_CW;
+    const int rows = (int) min<int64_t>(GRAM_RB, m - I0);
+    const int wlen = (int) min<int64_t>(GRAM_CW, m - W0);
+    for (int t = threadIdx.x; t < GRAM_CW; t += 256) cmax[t] = 0ull;
+    __syncthreads();
+    const int64_t base = rb_base[cell.I];
+    for (int t = wave; t < rows; t += 4) {
+        const int64_t a = base + rowoff[cell.rowoff + t], b = base + rowoff[cell.rowoff + t + 1];
+        double v = 0.0;
+        for (int64_t k = a + lane; k < b; k += 64) {
+            const double sk = fabs((double) ps[k]);
+            const int j = (int) pj[k];
+            if (sk > 0.0 && j < wlen) {  // pads: s = 0
+                v = max(v, sk);
+                atomicMax(&cmax[j], (unsigned long long) __double_as_longlong(sk));
+            }
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o));
+        if (lane == 0 && v > 0.0) atomicMax(&rs[I0 + t], (unsigned long long) __double_as_longlong(v));
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < wlen; t += 256)
+        if (cmax[t] != 0ull) atomicMax(&rs[W0 + t], cmax[t]);
+}
+
+// in place, the row's max |s| -> the bound on |c| over the row's pairs (form: 0 linear, 1 polynomial, 2 direct rbf,
+// 3 factored rbf); rows without pairs keep 0
+template <typename T>
+__global__ __launch_bounds__(256) void gram_cbound_kernel(int form, kfun<T> kf, int64_t m, double *__restrict__ rs) {
+    const int64_t t = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= m) return;
+    const double sm = rs[t];
+    if (!(sm > 0.0)) return;
+    double cb;
+    if (form == 3) {
+        cb = expm1(2.0 * fabs((double) kf.gamma) * sm);
+    } else if (form == 2) {
+        cb = 1.0;
+    } else if (form == 1) {
+        const double bse = fabs((double) kf.gamma) * sm + fabs((double) kf.coef0);
+        double a = 1.0, b = 1.0;
+        for (int q = 0; q < kf.degree; ++q) a *= bse, b *= fabs((double) kf.coef0);
+        cb = a + b;
+    } else {
+        cb = sm;
+    }
+    rs[t] = cb;
 }
 
 template <typename T>
@@ -1296,7 +1348,7 @@ void engine<T>::release_sparse_structures() {
     csr.spmv_csc = spmv_plan<T>{};
     csr.spmv_csr = spmv_plan<T>{};
     csr.pj.reset(), csr.ps.reset(), csr.rb_base.reset(), csr.rowoff.reset(), csr.cells.reset();
-    csr.slab_row.reset(), csr.slab_col.reset();
+    csr.slab_row.reset(), csr.slab_col.reset(), csr.cbnd.reset();
     csr.have_gram = false;
     csr.pairs = csr.slots = 0;
 }
@@ -1476,9 +1528,10 @@ void engine<T>::build_gram_blocks(const int64_t *cpos, int64_t max_inc) {
         MI_LAUNCH_CHECK();
     }
     // factored rbf c_ij = e_i e_j expm1(2 g s_ij): only while 2 g max|s_ij| <= 1. The fixed-point quantum
-    // of the K·p accumulators is set by the cell's bound expm1(2 g smax) max|e p|, which overestimates the
-    // actual terms (|e_i e_j expm1(2 g s)| <= 1) by up to expm1(2 g smax) e_i: above 1 the factored
-    // terms would lose digits to it, and the direct form exp(-g |x_i - x_j|^2) - e_i e_j (bound 1) is used
+    // of the K·p accumulators is set by the bound max_t expm1(2 g smax_t) |e_t p_t| over the cell's rows and
+    // partners (cbnd, below), which overestimates the actual terms (|e_i e_j expm1(2 g s)| <= 1) by up to
+    // expm1(2 g smax_t) e_i: above 1 the factored terms would lose digits to it, and the direct form
+    // exp(-g |x_i - x_j|^2) - e_i e_j (bound 1) is used
     csr.rbf_factored = false;
     if (kernel == 2) {
         std::vector<gram_cell> hc((size_t) csr.ncells);
@@ -1492,6 +1545,18 @@ void engine<T>::build_gram_blocks(const int64_t *cpos, int64_t max_inc) {
         csr.rbf_factored = rbf_form != 1 && u <= 1.0;
         // every pair's 2 g |s_ij| below the small-argument polynomial's bound -> KERNEL 4
         csr.rbf_small = u < expm1_small_bound<T>();
+    }
+    // the K·p kernel's term bound per row (its fixed-point quantum): |c| at the largest |s| the row meets
+    csr.cbnd.alloc(std::max<int64_t>(m, 1), stream);
+    if (csr.ncells > 0) {
+        hipLaunchKernelGGL(gram_row_smax_kernel<T>, dim3((unsigned) csr.ncells), dim3(256), 0, stream, csr.cells.get(),
+                           csr.rb_base.get(), csr.rowoff.get(), csr.pj.get(), csr.ps.get(), m,
+                           reinterpret_cast<unsigned long long *>(csr.cbnd.get()));
+        MI_LAUNCH_CHECK();
+        const int form = kernel == 2 ? (csr.rbf_factored ? 3 : 2) : kernel;
+        hipLaunchKernelGGL(gram_cbound_kernel<T>, dim3((unsigned) ceil_div(m, 256)), dim3(256), 0, stream, form, kf(), m,
+                           csr.cbnd.get());
+        MI_LAUNCH_CHECK();
     }
     MI_HIP_CHECK(hipStreamSynchronize(stream));
     csr.have_gram = true;
@@ -1581,8 +1646,8 @@ void engine<T>::sparse_dominant(const T *p, const cg_scalars<T> *status) {
     const dim3 grid((unsigned) csr.ncells);
     auto launch = [&](auto kern, int nt) {
         hipLaunchKernelGGL(kern, grid, dim3(nt), 0, stream, csr.cells.get(), csr.rb_base.get(), csr.rowoff.get(),
-                           csr.pj.get(), csr.ps.get(), norms.get(), csr.e.get(), p, csr.slab_row.get(),
-                           csr.slab_col.get(), m, csr.m_pad, kf(), kappa, status);
+                           csr.pj.get(), csr.ps.get(), norms.get(), csr.e.get(), csr.cbnd.get(), p,
+                           csr.slab_row.get(), csr.slab_col.get(), m, csr.m_pad, kf(), kappa, status);
     };
     auto pick = [&](auto abl) {
         constexpr int A = decltype(abl)::value;

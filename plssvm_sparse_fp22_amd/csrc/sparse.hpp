@@ -24,7 +24,7 @@ constexpr int GRAM_WG = 512;  // K·p workgroup size when two fit a CU (else 102
 struct gram_cell {
     int32_t I, W;
     int64_t rowoff;  // index in rowoff[] of the cell's row 0 (rowoff holds GRAM_RB + 1 entries per cell)
-    double smax;     // max |s_ij| over the cell's pairs (fixed-point bound of the K·p accumulators)
+    double smax;     // max |s_ij| over the cell's pairs (setup: the factored rbf form and its small-argument polynomial)
 };
 
 // ---- kernel expansion path (sparse poly / rbf), see DESIGN.md §5 and expand.hip ----------------------
@@ -126,6 +126,7 @@ struct csr_data {
     dev_buf<gram_cell> cells;
     dev_buf<T> slab_row;  // [nW][m_pad]
     dev_buf<T> slab_col;  // [nRB][m_pad]
+    dev_buf<double> cbnd; // [m]: bound on |c_ij| over row i's pairs (the K·p kernel's fixed-point quantum)
     dev_buf<T> ssc;       // device scalars: [0] = sum(e p) or sum(p)
 
     exp_data<T> ex;       // kernel expansion path (instead of the Gram pattern)
@@ -150,7 +151,7 @@ struct csr_data {
     int64_t bytes() const {
         return rowptr.bytes() + col.bytes() + val.bytes() + colptr.bytes() + crow.bytes() +
                cval.bytes() + spmv_csc.bytes() + spmv_csr.bytes() + rb_csr.bytes() + e.bytes() + pj.bytes() + ps.bytes() +
-               rb_base.bytes() + rowoff.bytes() + cells.bytes() + slab_row.bytes() + slab_col.bytes() + ex.bytes() +
+               rb_base.bytes() + rowoff.bytes() + cells.bytes() + slab_row.bytes() + slab_col.bytes() + cbnd.bytes() + ex.bytes() +
                seg.bytes() + ecb.bytes() + pne.bytes() + cjv.bytes() + otf_part.bytes();
     }
 };
