@@ -123,7 +123,11 @@ extern "C" {
  * binades (any RBF tile unless gamma is large) is kept as 52 mantissa bits + a 4-bit exponent offset per value below a
  * per-tile base exponent, 112 KiB instead of 128 KiB, and decoded bit-exactly while it is streamed; every other tile
  * (signs, zeros, denormals, inf, NaN, a wider span) and every fp32 tile keeps its raw record. Results are bitwise the
- * same either way. 0 = auto (on), 1 = off. Environment PLSSVM_MI_KP_PACK=0, read at setup, also turns it off. */
+ * same either way. A packable tile whose exponents are E - 1 and E only (E = its largest one; any tile of values in
+ * [0.5, 1], say) takes the narrow form instead: 52 mantissa bits + 1 exponent bit per value, 106 KiB.
+ * 0 = auto (narrow where eligible, else 7-byte, else raw), 1 = off (every record raw), 2 = 7-byte and raw only.
+ * Environment, read at setup: PLSSVM_MI_KP_PACK=0 also turns packing off, PLSSVM_MI_KP_NARROW=0 means 7-byte and raw
+ * only. */
 #define PLSSVM_MI_OPT_KP_PACK 8
 
 typedef struct plssvm_mi_ctx plssvm_mi_ctx;
@@ -402,6 +406,11 @@ typedef struct {
                                       result are those of the caller's features. Read-only */
 } plssvm_mi_info;
 PLSSVM_MI_API int plssvm_mi_get_info(const plssvm_mi_ctx *ctx, plssvm_mi_info *info);
+/* Of plssvm_mi_info.kp_cache_packed_tiles: the tiles stored at 53 bits per value (the narrow form of
+ * PLSSVM_MI_OPT_KP_PACK). 0 before the first K·p of a setup has filled the cache; read back from the device together
+ * with kp_cache_packed_tiles on the first request after that. An entry point of its own because plssvm_mi_info keeps
+ * its size and its last fields (tests/test_predict_multi_abi.py pins them). */
+PLSSVM_MI_API int plssvm_mi_get_kp_cache_narrow_tiles(const plssvm_mi_ctx *ctx, int64_t *narrow_tiles);
 
 #ifdef __cplusplus
 }

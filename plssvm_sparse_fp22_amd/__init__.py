@@ -217,8 +217,11 @@ class CSVM:
             self._check(L.plssvm_mi_set_option(self._ctx, _abi.OPT_CG_VARIANT, v))
         if kp_cache is not None:  # False: never store kernel-matrix tiles, see PLSSVM_MI_OPT_KP_CACHE
             self._check(L.plssvm_mi_set_option(self._ctx, _abi.OPT_KP_CACHE, 0 if kp_cache else 1))
-        if kp_pack is not None:  # False: stored fp64 tiles keep their raw 8-byte records, see PLSSVM_MI_OPT_KP_PACK
-            self._check(L.plssvm_mi_set_option(self._ctx, _abi.OPT_KP_PACK, 0 if kp_pack else 1))
+        if kp_pack is not None:  # False: stored fp64 tiles keep their raw 8-byte records; "wide": 7-byte records but no
+            # 53-bit ones; True: the default, see PLSSVM_MI_OPT_KP_PACK
+            if isinstance(kp_pack, str) and kp_pack != "wide":
+                raise ValueError(f"kp_pack must be True, False or 'wide', not {kp_pack!r}")
+            self._check(L.plssvm_mi_set_option(self._ctx, _abi.OPT_KP_PACK, 2 if kp_pack == "wide" else (0 if kp_pack else 1)))
         if multi_width is not None:  # 0 auto, 1 one vector at a time, n: at most n lanes, see PLSSVM_MI_OPT_MULTI_WIDTH
             self._check(L.plssvm_mi_set_option(self._ctx, _abi.OPT_MULTI_WIDTH, int(multi_width)))
         if sim_rank is not None:  # (rank, world): single-GPU test hook, see PLSSVM_MI_OPT_SIM_RANK
@@ -575,7 +578,15 @@ class CSVM:
     def info(self):
         inf = _abi.Info()
         self._check(_abi.lib().plssvm_mi_get_info(self._ctx, ctypes.byref(inf)))
-        return {k: getattr(inf, k) for k, _ in _abi.Info._fields_}
+        out = {k: getattr(inf, k) for k, _ in _abi.Info._fields_}
+        # the narrow tiles among kp_cache_packed_tiles: an entry point of its own (plssvm_mi_info keeps its size); a
+        # PLSSVM_MI_LIB build from before the narrow form has none and stores no such tile
+        narrow = ctypes.c_int64(0)
+        fn = getattr(_abi.lib(), "plssvm_mi_get_kp_cache_narrow_tiles", None)
+        if fn is not None:
+            self._check(fn(self._ctx, ctypes.byref(narrow)))
+        out["kp_cache_narrow_tiles"] = narrow.value
+        return out
 
     def get_num_devices(self):
         return self.world_size

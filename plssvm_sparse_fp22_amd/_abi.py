@@ -34,7 +34,11 @@ EXPORTS = (
     "plssvm_mi_comm_init_host", "plssvm_mi_kp_part", "plssvm_mi_set_progress", "plssvm_mi_comm_abort",
     "plssvm_mi_kp_multi", "plssvm_mi_solve_cg_multi", "plssvm_mi_learn_multi", "plssvm_mi_time_kp_multi",
     "plssvm_mi_predict_multi_dense", "plssvm_mi_predict_multi_csr", "plssvm_mi_get_predict_stats",
+    "plssvm_mi_get_kp_cache_narrow_tiles",
 )
+# the one entry point a PLSSVM_MI_LIB build may lack (a build from before the narrow record form, loaded for an A/B
+# run): CSVM.info() then reports kp_cache_narrow_tiles = 0, which is what such a build stores
+OPTIONAL_EXPORTS = ("plssvm_mi_get_kp_cache_narrow_tiles",)
 OPT_SIM_RANK = 2
 OPT_RBF_FORM = 3
 OPT_SPARSE_ALGO = 4
@@ -133,8 +137,11 @@ def _declare(L):
         "plssvm_mi_predict_multi_dense": ([P, P, I64, I64, P, P, I64, I64, P, I64], I),
         "plssvm_mi_predict_multi_csr": ([P, P, I64, I64, P, P, P, P, I, I64, I64, P, I64], I),
         "plssvm_mi_get_predict_stats": ([P, PI64], I),
+        "plssvm_mi_get_kp_cache_narrow_tiles": ([P, PI64], I),
     }
     for name, (args, res) in sig.items():
+        if name in OPTIONAL_EXPORTS and not hasattr(L, name):
+            continue
         f = getattr(L, name)
         f.argtypes = args
         f.restype = res

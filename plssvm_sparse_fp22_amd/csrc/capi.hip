@@ -116,7 +116,7 @@ int plssvm_mi_set_option(plssvm_mi_ctx *ctx, int key, int64_t value) {
             e.cg_variant = (int) value;
         } else if (key == PLSSVM_MI_OPT_KP_CACHE && value >= 0 && value <= 1) {
             e.kp_cache_opt = (int) value;
-        } else if (key == PLSSVM_MI_OPT_KP_PACK && value >= 0 && value <= 1) {
+        } else if (key == PLSSVM_MI_OPT_KP_PACK && value >= 0 && value <= 2) {
             e.kp_pack_opt = (int) value;
         } else if (key == PLSSVM_MI_OPT_MULTI_WIDTH && value >= 0 && value <= 1024) {
             e.multi_opt = (int) value;
@@ -490,6 +490,12 @@ int plssvm_mi_get_info(const plssvm_mi_ctx *cctx, plssvm_mi_info *info) {
         info->predict_algo = e.predict_algo;
         info->rbf_shift = (!e.sparse && e.shifted) ? 1 : 0;
     });
+}
+
+int plssvm_mi_get_kp_cache_narrow_tiles(const plssvm_mi_ctx *cctx, int64_t *narrow_tiles) {
+    if (!cctx || !narrow_tiles) return PLSSVM_MI_ERR_ARG;
+    auto *ctx = const_cast<plssvm_mi_ctx *>(cctx);
+    return ctx->call([&](auto &e) { *narrow_tiles = e.kcache_narrow(); });
 }
 
 }  // extern "C"

@@ -447,8 +447,9 @@ void engine<T>::kcache_setup() {
     kcache_tiles = 0;
     kcache.reset();
     kdesc.reset();
-    kpack_on = false;
+    kpack_on = 0;
     kpacked_host = -1;
+    knarrow_host = 0;
     const bool tiles_path = !factored() && (!sparse || csr.dense_on);  // kp_raw's launch_kp_tiles branch
     const char *ke = std::getenv("PLSSVM_MI_KP_CACHE");
     if (!tiles_path || kp_cache_opt == 1 || (ke != nullptr && std::atoi(ke) == 0) || kp_wgs <= 0 || m <= 0) return;
@@ -458,7 +459,7 @@ void engine<T>::kcache_setup() {
     if (tiles <= 0) return;
     try {
         kcache.alloc(tiles * KP_CACHE_REC, stream, false);
-        kdesc.alloc(tiles + 1, stream);  // every tile raw, no tile packed; outside the budget: T does not depend on it
+        kdesc.alloc(tiles + 2, stream);  // every tile raw, no tile packed or narrow; outside the budget: T does not depend on it
     } catch (const mi_error &) {
         (void) hipGetLastError();
         kcache.reset();
@@ -467,7 +468,9 @@ void engine<T>::kcache_setup() {
     }
     kcache_tiles = tiles;
     const char *pe = std::getenv("PLSSVM_MI_KP_PACK");
-    kpack_on = sizeof(T) == 8 && kp_pack_opt != 1 && !(pe != nullptr && std::atoi(pe) == 0);
+    const char *ne = std::getenv("PLSSVM_MI_KP_NARROW");
+    if (sizeof(T) == 8 && kp_pack_opt != 1 && !(pe != nullptr && std::atoi(pe) == 0))
+        kpack_on = (kp_pack_opt == 2 || (ne != nullptr && std::atoi(ne) == 0)) ? 1 : 2;
     pt.mark("kp cache alloc");
 }
 
@@ -488,18 +491,25 @@ void engine<T>::kp_tiles_now(const T *p, const cg_scalars<T> *status) {
     if (fill) kcache_valid = true;
 }
 
-// Tiles of the cache stored in the 7-byte form: the fill's counter, copied back once, on the first request after it
+// Tiles of the cache stored in a packed form (7-byte or 53-bit), and those of them in the 53-bit form: the fill's two
+// counters, copied back together, once, on the first request after it
 template <typename T>
 int64_t engine<T>::kcache_packed() {
-    if (!kcache_valid || kcache_tiles <= 0 || !kpack_on) return 0;
+    if (!kcache_valid || kcache_tiles <= 0 || kpack_on == 0) return 0;
     if (kpacked_host < 0) {
-        int32_t c = 0;
+        int32_t c[2] = { 0, 0 };
         MI_HIP_CHECK(hipSetDevice(device));
-        MI_HIP_CHECK(hipMemcpyAsync(&c, kdesc.get() + kcache_tiles, sizeof(c), hipMemcpyDeviceToHost, stream));
+        MI_HIP_CHECK(hipMemcpyAsync(c, kdesc.get() + kcache_tiles, sizeof(c), hipMemcpyDeviceToHost, stream));
         MI_HIP_CHECK(hipStreamSynchronize(stream));
-        kpacked_host = c;
+        kpacked_host = c[0];
+        knarrow_host = c[1];
     }
     return kpacked_host;
+}
+
+template <typename T>
+int64_t engine<T>::kcache_narrow() {
+    return kcache_packed() > 0 ? knarrow_host : 0;
 }
 
 template <typename T>

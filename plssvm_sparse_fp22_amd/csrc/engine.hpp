@@ -103,14 +103,18 @@ struct engine : engine_base {
     dev_buf<T> kcache;
     int64_t kcache_tiles = 0;
     bool kcache_valid = false;
-    // 7-byte records (kp_pack.hpp): one descriptor per cached tile — raw, or the tile's base exponent — written by
-    // the fill, read by every KP_LOAD workgroup; kdesc[kcache_tiles] counts the packed tiles. Allocated and dropped
-    // with the cache. fp32 records are never packed.
-    int kp_pack_opt = 0;  // PLSSVM_MI_OPT_KP_PACK: 0 auto (fp64: on), 1 off; env PLSSVM_MI_KP_PACK=0 at setup: off
+    // 7-byte and 53-bit records (kp_pack.hpp, kp_narrow.hpp): one descriptor per cached tile — raw, or the tile's
+    // largest exponent, flagged for the 53-bit form — written by the fill, read by every KP_LOAD workgroup;
+    // kdesc[kcache_tiles] counts the packed tiles of both forms, kdesc[kcache_tiles + 1] the narrow ones. Allocated and
+    // dropped with the cache. fp32 records are never packed.
+    int kp_pack_opt = 0;  // PLSSVM_MI_OPT_KP_PACK: 0 auto (fp64: narrow where eligible, else 7-byte, else raw), 1 off,
+                          // 2 7-byte only; env at setup: PLSSVM_MI_KP_PACK=0 off, PLSSVM_MI_KP_NARROW=0 7-byte only
     dev_buf<int32_t> kdesc;
-    bool kpack_on = false;        // this setup's fill may pack
-    int64_t kpacked_host = -1;    // the counter, read back on the first request after the fill (-1: not yet)
+    int kpack_on = 0;             // this setup's fill: 0 every tile raw, 1 raw or 7-byte, 2 all three forms
+    int64_t kpacked_host = -1;    // the counters, read back together on the first request after the fill (-1: not yet)
+    int64_t knarrow_host = 0;
     int64_t kcache_packed();
+    int64_t kcache_narrow();
     void kcache_setup();  // after the setup's other allocations
     void kp_tiles_now(const T *p, const cg_scalars<T> *status);  // the tile launches of one K·p
     int64_t r0 = 0, r1 = 0, chunk = 0;    // rows owned by this rank (factored / sparse row paths)

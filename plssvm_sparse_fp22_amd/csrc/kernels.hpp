@@ -73,14 +73,16 @@ void kp_tile_offsets(int64_t nb, int64_t s0, int64_t nsuper, std::vector<int32_t
 enum kp_tile_mode { KP_COMPUTE = 0, KP_COMPUTE_STORE = 1, KP_LOAD = 2 };
 constexpr int64_t KP_CACHE_REC = (int64_t) KP_TILE * KP_TILE;
 // tiles [0, cached) from / to kcache (fill: computed and stored, else loaded), tiles [cached, wgs) computed.
-// fp64 records come in two forms (kp_pack.hpp): kdesc[tile] says raw (0) or holds the base exponent of a tile stored
-// at 7 bytes per value in the first 112 KiB of its record; the fill writes it (pack false: every tile raw) and adds
-// one to *kcount per packed tile, KP_LOAD reads it. Needed whenever cached > 0 in fp64; fp32 ignores it.
+// fp64 records come in three forms (kp_pack.hpp, kp_narrow.hpp): kdesc[tile] says raw (0), or holds the largest
+// exponent E of a tile stored at 7 bytes per value in the first 112 KiB of its record, or E | KP_NARROW_FLAG for a tile
+// stored at 53 bits per value in the first 106 KiB; the fill writes it (pack 0: every tile raw, 1: raw or 7-byte,
+// 2: all three) and adds one to kcount[0] per packed tile of either form and one to kcount[1] per narrow tile, KP_LOAD
+// reads it. Needed whenever cached > 0 in fp64; fp32 ignores it.
 template <typename T>
 void launch_kp_tiles(kfun<T> kf, const T *XT, const T *norms, const T *p, T *partial, int64_t n_pad, int64_t d_pad,
                      int64_t nb, int64_t s0, int64_t nsuper, const int32_t *wg_off, int64_t wgs,
                      const cg_scalars<T> *status, hipStream_t s, T *kcache = nullptr, int64_t cached = 0,
-                     bool fill = false, int32_t *kdesc = nullptr, int32_t *kcount = nullptr, bool pack = false);
+                     bool fill = false, int32_t *kdesc = nullptr, int32_t *kcount = nullptr, int pack = 0);
 
 // The same tiles for nvec vectors at once (2 .. KP_MULTI_W; 1 is legal): vector c is p + c * pstride, its slab
 // partial + c * sstride, its stop flag status[c] (status null: none; a vector whose flag says converged is skipped and

@@ -22,6 +22,7 @@
 #include "kernels.hpp"
 #include "kp_device.hpp"
 #include "kp_pack.hpp"
+#include "kp_narrow.hpp"
 
 namespace plssvm_mi {
 
@@ -90,12 +91,14 @@ constexpr int KP_OFF_PAN = 4 * KP_TILE;
 constexpr int KP_RSTR = 17, KP_RHALF = KP_TILE * KP_RSTR + 1, KP_CSTR = 5;
 
 // The fp64 KP_LOAD workgroup: the tile's record -> registers -> the "times p" epilogue of kp_tile_kernel (the same
-// fma chains, LDS park and fixed-order sums, so the slab record is bitwise the computed one). PACKED: the record is
-// the 7-byte form of kp_pack.hpp — 28 dwordx4 per lane instead of 32, each value's high dword rebuilt from its
-// 24-bit word and the tile's base just before its fma. All of the lane's loads are issued before the first use: the
-// whole record (112 or 128 KiB) is in flight. MULTI: the values are decoded once, then multiplied with every live
-// vector as in kp_tile_kernel's MULTI epilogue.
-template <bool PACKED, bool MULTI>
+// fma chains, LDS park and fixed-order sums, so the slab record is bitwise the computed one). FORM: KP_FORM_WIDE, the
+// record is the 7-byte form of kp_pack.hpp — 28 dwordx4 per lane instead of 32, each value's high dword rebuilt from
+// its 24-bit word and the tile's base just before its fma; KP_FORM_NARROW, the 53-bit form of kp_narrow.hpp — 26
+// dwordx4 and one dwordx2 per lane, the high dword rebuilt from its 21-bit word of the lane's bit stream. All of the
+// lane's loads are issued before the first use: the whole record (106, 112 or 128 KiB) is in flight. MULTI: the values
+// are decoded once, then multiplied with every live vector as in kp_tile_kernel's MULTI epilogue.
+constexpr int KP_FORM_RAW = 0, KP_FORM_WIDE = 1, KP_FORM_NARROW = 2;
+template <int FORM, bool MULTI>
 __device__ __forceinline__ void kp_load_f64(const double *__restrict__ kcache, int64_t wg, uint32_t base,
                                             const double *__restrict__ p, double *__restrict__ partial, double *smem,
                                             int tid, int lane, int wr, int wc, bool diag, int64_t pidx, unsigned live,
@@ -107,9 +110,32 @@ __device__ __forceinline__ void kp_load_f64(const double *__restrict__ kcache, i
     // staging barrier below must not wait for the record
     int c = MULTI ? __builtin_ctz(live) : 0;
     double pnext = p[MULTI ? c * pstride + pidx : pidx];
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    constexpr bool PACKED = FORM == KP_FORM_WIDE, NARROW = FORM == KP_FORM_NARROW;
     u32x4 kq[PACKED ? KP_PACK_GROUPS : 1];
-    f64x2 kld[PACKED ? 1 : 32];
-    if constexpr (PACKED) {
+    f64x2 kld[FORM == KP_FORM_RAW ? 32 : 1];
+    u32x4 nl[NARROW ? 16 : 1], nh[NARROW ? KP_NARROW_HGROUPS - 1 : 1];  // L0 .. L15, H0 .. H9
+    u32x2 nh10 = { 0u, 0u };                                            // H10: stream dwords 40 and 41
+    if constexpr (NARROW) {
+        // record order: L_k, then the H group that row k is the first to need (at most one: kp_narrow_hi_row grows)
+        const uint32_t *rec0 = reinterpret_cast<const uint32_t *>(kcache + wg * KP_CACHE_REC);
+        const u32x4 *rec = reinterpret_cast<const u32x4 *>(rec0) + tid;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            nl[k] = KP_LOAD_NT ? __builtin_nontemporal_load(rec + kp_narrow_lo_group(k) * 256) : rec[kp_narrow_lo_group(k) * 256];
+            if constexpr (!MULTI) __builtin_amdgcn_sched_barrier(0);  // issued in record order: they return in order
+#pragma unroll
+            for (int h = 0; h < KP_NARROW_HGROUPS - 1; ++h) {
+                if (kp_narrow_hi_row(h) == k) {
+                    nh[h] = KP_LOAD_NT ? __builtin_nontemporal_load(rec + kp_narrow_hi_group(h) * 256) : rec[kp_narrow_hi_group(h) * 256];
+                    if constexpr (!MULTI) __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+        const u32x2 *rec2 = reinterpret_cast<const u32x2 *>(rec0 + kp_narrow_group_dword(KP_NARROW_GROUPS - 1, 0)) + tid;
+        nh10 = KP_LOAD_NT ? __builtin_nontemporal_load(rec2) : *rec2;
+        if constexpr (!MULTI) __builtin_amdgcn_sched_barrier(0);
+    } else if constexpr (PACKED) {
         const u32x4 *rec = reinterpret_cast<const u32x4 *>(kcache + wg * KP_CACHE_REC) + tid;
 #pragma unroll
         for (int g = 0; g < KP_PACK_GROUPS; ++g) {
@@ -129,8 +155,13 @@ __device__ __forceinline__ void kp_load_f64(const double *__restrict__ kcache, i
     // (left to itself the scheduler gathers the integer decode of all rows behind the first LDS read: vmcnt(1) at once)
     if constexpr (!MULTI) __builtin_amdgcn_sched_barrier(0);
     // value nt of row (mt, r); every index is a constant once the loops are unrolled
+    auto nword = [&](int j) -> uint32_t { return j < 40 ? nh[j >> 2][j & 3] : nh10[j & 1]; };  // dword j of the bit stream
     auto kval = [&](int mt, int r, int nt) -> double {
-        if constexpr (PACKED) {
+        if constexpr (NARROW) {
+            const int v = (mt * 4 + r) * 4 + nt, j = kp_narrow_word(v);
+            const uint32_t hi = kp_narrow_unpack(v, nword(j), nword(kp_narrow_straddles(v) ? j + 1 : j), base);
+            return __hiloint2double((int) hi, (int) nl[mt * 4 + r][nt]);
+        } else if constexpr (PACKED) {
             const int d0 = 3 * r;
             const uint32_t lo = kq[kp_pack_lo_group(mt, r)][nt];
             const uint32_t hi = kp_unpack4(nt, kq[kp_pack_hi_group(mt, d0)][d0 & 3], kq[kp_pack_hi_group(mt, d0 + 1)][(d0 + 1) & 3],
@@ -252,10 +283,11 @@ __device__ __forceinline__ void kp_load_f64(const double *__restrict__ kcache, i
 // on — the same fma order, LDS park and sums, so the slab record is bitwise the computed one. A cache record is
 // in register layout, [value group][thread][VEC]: a lane's 64 values in (mt, r, nt) order, 16 bytes per lane and
 // group, so every wave-instruction moves one contiguous KiB. wg_base: the first workgroup (tile) of this launch.
-// fp64 records come raw or in the 7-byte form of kp_pack.hpp, per tile (kdesc[wg]: 0 = raw, else the tile's base
-// exponent): the fp64 KP_COMPUTE_STORE instance finds the tile's exponent range, writes the descriptor, counts the
-// packed tiles in *kcount (pack = 0: every tile raw) and stores either form; the fp64 KP_LOAD instance is kp_load_f64
-// above, so the KP_LOAD statements in this body serve fp32 only. fp32 records are always raw.
+// fp64 records come raw, in the 7-byte form of kp_pack.hpp or in the 53-bit form of kp_narrow.hpp, per tile (kdesc[wg]:
+// 0 = raw, the tile's largest exponent E = 7-byte, E | KP_NARROW_FLAG = narrow): the fp64 KP_COMPUTE_STORE instance
+// finds the tile's exponent range, writes the descriptor, counts the packed tiles of both forms in kcount[0] and the
+// narrow ones in kcount[1] (pack = 0: every tile raw, 1: no narrow tile) and stores the form; the fp64 KP_LOAD
+// instance is kp_load_f64 above, so the KP_LOAD statements in this body serve fp32 only. fp32 records are always raw.
 //
 // MULTI: nvec (<= KP_MULTI_W) vectors per visit of a tile (the single-vector instances ignore nvec and the
 // strides). Vector c is p + c * pstride, its slab partial + c * sstride, its stop flag status[c]. The tile's kernel
@@ -346,12 +378,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_wav
 
     const int64_t pidx = (tid < KP_TILE) ? I0 + tid : J0 + (tid - KP_TILE);
     if constexpr (PACK_LOAD) {
-        if (desc != KP_PACK_RAW)
-            kp_load_f64<true, MULTI>(kcache, wg, kp_pack_base(desc), p, partial, smem, tid, lane, wr, wc, diag, pidx, live,
-                                     pstride, sstride);
+        if (kp_desc_is_narrow(desc))
+            kp_load_f64<KP_FORM_NARROW, MULTI>(kcache, wg, kp_narrow_base(kp_desc_exp(desc)), p, partial, smem, tid, lane, wr, wc,
+                                               diag, pidx, live, pstride, sstride);
+        else if (desc != KP_PACK_RAW)
+            kp_load_f64<KP_FORM_WIDE, MULTI>(kcache, wg, kp_pack_base(desc), p, partial, smem, tid, lane, wr, wc, diag, pidx, live,
+                                             pstride, sstride);
         else
-            kp_load_f64<false, MULTI>(kcache, wg, 0u, p, partial, smem, tid, lane, wr, wc, diag, pidx, live, pstride,
-                                      sstride);
+            kp_load_f64<KP_FORM_RAW, MULTI>(kcache, wg, 0u, p, partial, smem, tid, lane, wr, wc, diag, pidx, live, pstride,
+                                            sstride);
         return;
     }
     acc_t acc[4][4];
@@ -494,15 +529,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_wav
             __syncthreads();  // every wave is done with the last K chunk: the panels become reduction buffers
             mn = min(min(pk_red[0], pk_red[2]), min(pk_red[4], pk_red[6]));
             mx = max(max(pk_red[1], pk_red[3]), max(pk_red[5], pk_red[7]));
-            pk_desc = __builtin_amdgcn_readfirstlane(pack ? kp_pack_desc(mn, mx) : KP_PACK_RAW);
+            pk_desc = __builtin_amdgcn_readfirstlane(pack >= 2 ? kp_narrow_desc(mn, mx) : pack ? kp_pack_desc(mn, mx) : KP_PACK_RAW);
             if (tid == 0) {
                 kdesc[wg] = (int32_t) pk_desc;
-                if (pk_desc != KP_PACK_RAW) atomicAdd(kcount, 1);  // one per packed tile
+                if (pk_desc != KP_PACK_RAW) atomicAdd(kcount, 1);            // one per packed tile, either form
+                if (kp_desc_is_narrow(pk_desc)) atomicAdd(kcount + 1, 1);  // one per narrow tile
             }
         } else {
             __syncthreads();  // every wave is done with the last K chunk: the panels become reduction buffers
         }
-        const uint32_t pk_base = kp_pack_base(pk_desc);
+        const bool pk_narrow = kp_desc_is_narrow(pk_desc);  // uniform
+        const uint32_t pk_base = pk_narrow ? kp_narrow_base(kp_desc_exp(pk_desc)) : kp_pack_base(pk_desc);
+        // narrow form: the lane's bit stream of 21-bit words, carried across the rows; unrolled, every dword is a value
+        // of its own that lives from the first word that reaches it to the store of its group
+        uint32_t pk_nw[PACK_STORE ? KP_NARROW_HDW : 1];
         T *rowp = smem + OFF_PAN + wc * RHALF;
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
@@ -533,7 +573,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_wav
                 rowp[il * RSTR + (lane & 15)] = s;
                 if constexpr (PACK_STORE) {
                     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-                    if (pk_desc != KP_PACK_RAW) {  // uniform
+                    if (pk_narrow) {
+                        uint32_t *rec0 = reinterpret_cast<uint32_t *>(kcache + wg * KP_CACHE_REC);
+                        const int row = mt * 4 + r;  // a constant once unrolled, and with it every position below
+                        u32x4 lo;
+#pragma unroll
+                        for (int nt = 0; nt < 4; ++nt) {
+                            lo[nt] = (uint32_t) __double2loint((double) kvs[nt]);
+                            kp_narrow_put(row * 4 + nt, kp_narrow_h21((uint32_t) __double2hiint((double) kvs[nt]), pk_base), pk_nw);
+                        }
+                        *reinterpret_cast<u32x4 *>(rec0 + kp_narrow_group_dword(kp_narrow_lo_group(row), tid)) = lo;
+#pragma unroll
+                        for (int h = 0; h < KP_NARROW_HGROUPS; ++h) {  // the groups this row completed
+                            if (h < kp_narrow_hi_done(row) && (row == 0 || h >= kp_narrow_hi_done(row - 1))) {
+                                uint32_t *at = rec0 + kp_narrow_group_dword(kp_narrow_hi_group(h), tid);
+                                if (h < KP_NARROW_HGROUPS - 1) {
+                                    *reinterpret_cast<u32x4 *>(at) = u32x4{ pk_nw[4 * h], pk_nw[4 * h + 1], pk_nw[4 * h + 2], pk_nw[4 * h + 3] };
+                                } else {
+                                    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+                                    *reinterpret_cast<u32x2 *>(at) = u32x2{ pk_nw[4 * h], pk_nw[4 * h + 1] };
+                                }
+                            }
+                        }
+                    } else if (pk_desc != KP_PACK_RAW) {  // uniform
                         u32x4 *rec = reinterpret_cast<u32x4 *>(kcache + wg * KP_CACHE_REC) + tid;
                         uint32_t hi[4];
                         u32x4 lo;
@@ -750,12 +812,12 @@ namespace {
 template <typename T, int MODE>
 void launch_kp_mode(kfun<T> kf, const T *XT, const T *norms, const T *p, T *partial, int64_t n_pad, int64_t d_pad,
                     int64_t nb, int64_t s0, int64_t nsuper, const int32_t *wg_off, int64_t base, int64_t count,
-                    const cg_scalars<T> *status, T *kcache, int32_t *kdesc, int32_t *kcount, bool pack, hipStream_t s) {
+                    const cg_scalars<T> *status, T *kcache, int32_t *kdesc, int32_t *kcount, int pack, hipStream_t s) {
     if (count <= 0) return;
     const dim3 grid((unsigned) count), block(256);
 #define KP_LAUNCH(KERNEL)                                                                                         \
     hipLaunchKernelGGL((kp_tile_kernel<T, KERNEL, MODE>), grid, block, 0, s, kf, XT, norms, p, partial, n_pad, d_pad, \
-                       nb, s0, nsuper, wg_off, status, base, kcache, 1, (int64_t) 0, (int64_t) 0, kdesc, kcount, pack ? 1 : 0)
+                       nb, s0, nsuper, wg_off, status, base, kcache, 1, (int64_t) 0, (int64_t) 0, kdesc, kcount, pack)
     if constexpr (MODE == KP_LOAD) {
         KP_LAUNCH(0);  // one instance per real type: the stored values are past the kernel function
     } else {
@@ -778,7 +840,7 @@ template <typename T>
 void launch_kp_tiles(kfun<T> kf, const T *XT, const T *norms, const T *p, T *partial, int64_t n_pad, int64_t d_pad,
                      int64_t nb, int64_t s0, int64_t nsuper, const int32_t *wg_off, int64_t wgs,
                      const cg_scalars<T> *status, hipStream_t s, T *kcache, int64_t cached, bool fill, int32_t *kdesc,
-                     int32_t *kcount, bool pack) {
+                     int32_t *kcount, int pack) {
     if (nsuper <= 0 || nb <= 0 || wgs <= 0) return;
     // 32-bit DMA offsets inside a chunk (kp_tile_kernel): (BK - 1) rows of n_pad plus a tile row
     if ((int64_t) kp_dpad<T>() * n_pad * (int64_t) sizeof(T) >= ((int64_t) 1 << 31))
@@ -792,9 +854,9 @@ void launch_kp_tiles(kfun<T> kf, const T *XT, const T *norms, const T *p, T *par
                                             status, kcache, kdesc, kcount, pack, s);
     else
         launch_kp_mode<T, KP_LOAD>(kf, XT, norms, p, partial, n_pad, d_pad, nb, s0, nsuper, wg_off, 0, cached, status,
-                                   kcache, kdesc, kcount, false, s);
+                                   kcache, kdesc, kcount, 0, s);
     launch_kp_mode<T, KP_COMPUTE>(kf, XT, norms, p, partial, n_pad, d_pad, nb, s0, nsuper, wg_off, cached, wgs - cached,
-                                  status, nullptr, nullptr, nullptr, false, s);
+                                  status, nullptr, nullptr, nullptr, 0, s);
 }
 
 // The batched form: nvec vectors p + c * pstride into the slabs partial + c * sstride, stop flags status[c] (null:
@@ -847,7 +909,7 @@ void launch_kp_reduce(const T *partial, int64_t nb, int64_t m, int64_t s0, int64
 #define INST(T)                                                                                                  \
     template void launch_kp_tiles<T>(kfun<T>, const T *, const T *, const T *, T *, int64_t, int64_t, int64_t, \
                                      int64_t, int64_t, const int32_t *, int64_t, const cg_scalars<T> *,        \
-                                     hipStream_t, T *, int64_t, bool, int32_t *, int32_t *, bool);     \
+                                     hipStream_t, T *, int64_t, bool, int32_t *, int32_t *, int);      \
     template void launch_kp_tiles_multi<T>(kfun<T>, const T *, const T *, const T *, int64_t, T *, int64_t, int,  \
                                            int64_t, int64_t, int64_t, int64_t, int64_t, const int32_t *, int64_t,  \
                                            const cg_scalars<T> *, hipStream_t, const T *, int64_t,     \
