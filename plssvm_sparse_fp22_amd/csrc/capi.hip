@@ -115,9 +115,9 @@ int plssvm_mi_set_option(plssvm_mi_ctx *ctx, int key, int64_t value) {
         } else if (key == PLSSVM_MI_OPT_CG_VARIANT && value >= 0 && value <= 2) {
             e.cg_variant = (int) value;
         } else if (key == PLSSVM_MI_OPT_KP_CACHE && value >= 0 && value <= 1) {
-            e.kp_cache_opt = (int) value;
+            e.kc.cache_opt = (int) value;
         } else if (key == PLSSVM_MI_OPT_KP_PACK && value >= 0 && value <= 2) {
-            e.kp_pack_opt = (int) value;
+            e.kc.pack_opt = (int) value;
         } else if (key == PLSSVM_MI_OPT_MULTI_WIDTH && value >= 0 && value <= 1024) {
             e.multi_opt = (int) value;
         } else {
@@ -483,10 +483,10 @@ int plssvm_mi_get_info(const plssvm_mi_ctx *cctx, plssvm_mi_info *info) {
         info->exp_dot2 = e.csr.ex.on && e.csr.ex.hbf16 && e.csr.ex.dot2 && sizeof(e.gamma) == 4 && plssvm_mi::exp_dot2_built() ? 1 : 0;
         info->centered = e.ctr_active() ? 1 : 0;
         info->exp_lt = e.csr.ex.on && e.csr.ex.lt ? 1 : 0;
-        info->kp_cache_tiles = e.kcache_tiles;
-        info->kp_cache_bytes = e.kcache.bytes();
+        info->kp_cache_tiles = e.kc.tiles;
+        info->kp_cache_bytes = e.kc.rec.bytes();
         info->multi_width = e.multi_width_next();
-        info->kp_cache_packed_tiles = e.kcache_packed();
+        info->kp_cache_packed_tiles = e.kc.packed(e);
         info->predict_algo = e.predict_algo;
         info->rbf_shift = (!e.sparse && e.shifted) ? 1 : 0;
     });
@@ -495,7 +495,7 @@ int plssvm_mi_get_info(const plssvm_mi_ctx *cctx, plssvm_mi_info *info) {
 int plssvm_mi_get_kp_cache_narrow_tiles(const plssvm_mi_ctx *cctx, int64_t *narrow_tiles) {
     if (!cctx || !narrow_tiles) return PLSSVM_MI_ERR_ARG;
     auto *ctx = const_cast<plssvm_mi_ctx *>(cctx);
-    return ctx->call([&](auto &e) { *narrow_tiles = e.kcache_narrow(); });
+    return ctx->call([&](auto &e) { *narrow_tiles = e.kc.narrow(e); });
 }
 
 }  // extern "C"

@@ -105,8 +105,7 @@ engine<T>::~engine() {
     if (blas) (void) rocblas_destroy_handle(blas);
     XT.reset();
     partial.reset();
-    kcache.reset();
-    kdesc.reset();
+    kc.reset();
     if (stream) (void) hipStreamDestroy(stream);
 }
 
@@ -418,7 +417,7 @@ void engine<T>::finish_setup() {
     raw.alloc(vec_len, stream);
     w.alloc(std::max<int64_t>(d_pad, 1), stream);
     MI_HIP_CHECK(hipStreamSynchronize(stream));
-    kcache_setup();
+    kc.setup(*this);
     have_data = true;
     have_q = false;
     q_gen = false;
@@ -438,39 +437,43 @@ void engine<T>::tiles_upload() {
     MI_HIP_CHECK(hipStreamSynchronize(stream));
 }
 
+template <typename T>
+void engine<T>::tile_cache::reset() {
+    rec.reset();
+    desc.reset();
+    tiles = 0;
+    valid = false;
+    pack = 0;
+    packed_host = -1;
+    narrow_host = 0;
+}
+
 // The tile cache of this setup: as many of the rank's tiles as the memory budget holds, none for a path that does not
 // run the tile kernel. The records of an earlier setup are dropped first (their data is gone), nothing is written
 // here: the first K·p without a stop flag fills them (kp_tiles_now). No room, or an allocation that fails: no cache.
 template <typename T>
-void engine<T>::kcache_setup() {
-    kcache_valid = false;
-    kcache_tiles = 0;
-    kcache.reset();
-    kdesc.reset();
-    kpack_on = 0;
-    kpacked_host = -1;
-    knarrow_host = 0;
-    const bool tiles_path = !factored() && (!sparse || csr.dense_on);  // kp_raw's launch_kp_tiles branch
+void engine<T>::tile_cache::setup(const engine &e) {
+    reset();
+    const bool tiles_path = !e.factored() && (!e.sparse || e.csr.dense_on);  // kp_raw's launch_kp_tiles branch
     const char *ke = std::getenv("PLSSVM_MI_KP_CACHE");
-    if (!tiles_path || kp_cache_opt == 1 || (ke != nullptr && std::atoi(ke) == 0) || kp_wgs <= 0 || m <= 0) return;
+    if (!tiles_path || cache_opt == 1 || (ke != nullptr && std::atoi(ke) == 0) || e.kp_wgs <= 0 || e.m <= 0) return;
     phase_timer pt;
     const int64_t rec_bytes = KP_CACHE_REC * (int64_t) sizeof(T);
-    const int64_t tiles = std::min<int64_t>(kp_wgs, mem_budget() / rec_bytes);
-    if (tiles <= 0) return;
+    const int64_t fit = std::min<int64_t>(e.kp_wgs, e.mem_budget() / rec_bytes);
+    if (fit <= 0) return;
     try {
-        kcache.alloc(tiles * KP_CACHE_REC, stream, false);
-        kdesc.alloc(tiles + 2, stream);  // every tile raw, no tile packed or narrow; outside the budget: T does not depend on it
+        rec.alloc(fit * KP_CACHE_REC, e.stream, false);
+        desc.alloc(fit + 2, e.stream);  // every tile raw, no tile packed or narrow; outside the budget: T does not depend on it
     } catch (const mi_error &) {
         (void) hipGetLastError();
-        kcache.reset();
-        kdesc.reset();
+        reset();
         return;
     }
-    kcache_tiles = tiles;
+    tiles = fit;
     const char *pe = std::getenv("PLSSVM_MI_KP_PACK");
     const char *ne = std::getenv("PLSSVM_MI_KP_NARROW");
-    if (sizeof(T) == 8 && kp_pack_opt != 1 && !(pe != nullptr && std::atoi(pe) == 0))
-        kpack_on = (kp_pack_opt == 2 || (ne != nullptr && std::atoi(ne) == 0)) ? 1 : 2;
+    if (sizeof(T) == 8 && pack_opt != 1 && !(pe != nullptr && std::atoi(pe) == 0))
+        pack = (pack_opt == 2 || (ne != nullptr && std::atoi(ne) == 0)) ? 1 : 2;
     pt.mark("kp cache alloc");
 }
 
@@ -480,36 +483,29 @@ void engine<T>::kcache_setup() {
 template <typename T>
 void engine<T>::kp_tiles_now(const T *p, const cg_scalars<T> *status) {
     bool fill = false;
-    if (kcache_tiles > 0 && !kcache_valid && status == nullptr) {
+    if (kc.tiles > 0 && !kc.valid && status == nullptr) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         MI_HIP_CHECK(hipStreamIsCapturing(stream, &cs));
         fill = cs == hipStreamCaptureStatusNone;
     }
-    const int64_t cached = (kcache_valid || fill) ? kcache_tiles : 0;
-    launch_kp_tiles<T>(kf(), XT.get(), norms.get(), p, partial.get(), n_pad, d_pad, nb, t0, t1 - t0, kp_wgoff.get(), kp_wgs,
-                       status, stream, kcache.get(), cached, fill, kdesc.get(), kdesc.get() + kcache_tiles, kpack_on);
-    if (fill) kcache_valid = true;
+    launch_kp_tiles<T>(kp_geometry(), p, partial.get(), status, stream, kc.view(fill), fill);
+    if (fill) kc.valid = true;
 }
 
-// Tiles of the cache stored in a packed form (7-byte or 53-bit), and those of them in the 53-bit form: the fill's two
+// Tiles of the cache stored in a packed form (wide or narrow), and those of them in the narrow form: the fill's two
 // counters, copied back together, once, on the first request after it
 template <typename T>
-int64_t engine<T>::kcache_packed() {
-    if (!kcache_valid || kcache_tiles <= 0 || kpack_on == 0) return 0;
-    if (kpacked_host < 0) {
+int64_t engine<T>::tile_cache::packed(const engine &e) {
+    if (!valid || tiles <= 0 || pack == 0) return 0;
+    if (packed_host < 0) {
         int32_t c[2] = { 0, 0 };
-        MI_HIP_CHECK(hipSetDevice(device));
-        MI_HIP_CHECK(hipMemcpyAsync(c, kdesc.get() + kcache_tiles, sizeof(c), hipMemcpyDeviceToHost, stream));
-        MI_HIP_CHECK(hipStreamSynchronize(stream));
-        kpacked_host = c[0];
-        knarrow_host = c[1];
+        MI_HIP_CHECK(hipSetDevice(e.device));
+        MI_HIP_CHECK(hipMemcpyAsync(c, desc.get() + tiles, sizeof(c), hipMemcpyDeviceToHost, e.stream));
+        MI_HIP_CHECK(hipStreamSynchronize(e.stream));
+        packed_host = c[0];
+        narrow_host = c[1];
     }
-    return kpacked_host;
-}
-
-template <typename T>
-int64_t engine<T>::kcache_narrow() {
-    return kcache_packed() > 0 ? knarrow_host : 0;
+    return packed_host;
 }
 
 template <typename T>
@@ -1054,8 +1050,7 @@ void engine<T>::time_kp(int reps, double *ms_kp, double *ms_dom) {
         } else if (factored()) {
             launch_gemv_n<T>(XT.get(), n_pad, d, r0, r1, w.get(), raw.get(), nullptr, stream);
         } else {
-            launch_kp_tiles<T>(kf(), XT.get(), norms.get(), pv.get(), partial.get(), n_pad, d_pad, nb, t0, t1 - t0, kp_wgoff.get(), kp_wgs,
-                               nullptr, stream);
+            launch_kp_tiles<T>(kp_geometry(), pv.get(), partial.get(), nullptr, stream);
         }
         MI_HIP_CHECK(hipEventRecord(d1, stream));
         MI_HIP_CHECK(hipEventSynchronize(d1));
@@ -1140,10 +1135,8 @@ int engine<T>::multi_lanes() {
 // The stored records are streamed once they are filled; filling them is the single-vector path's job.
 template <typename T>
 void engine<T>::tiles_multi(int kind, int c0, int nvec, bool flags) {
-    launch_kp_tiles_multi<T>(kf(), XT.get(), norms.get(), lane_v(kind, c0), lanes.vstride,
-                             lanes.slab.get() + (int64_t) c0 * lanes.sstride, lanes.sstride, nvec, n_pad, d_pad, nb, t0,
-                             t1 - t0, kp_wgoff.get(), kp_wgs, flags ? lanes.sc.get() + c0 : nullptr, stream, kcache.get(),
-                             kcache_valid ? kcache_tiles : 0, kdesc.get());
+    launch_kp_tiles_multi<T>(kp_geometry(), lane_v(kind, c0), lanes.vstride, lanes.slab.get() + (int64_t) c0 * lanes.sstride,
+                             lanes.sstride, nvec, flags ? lanes.sc.get() + c0 : nullptr, stream, kc.view());
 }
 
 // kp_device for lanes [c0, c0 + nvec) with one pass over the tiles (engine.hpp)
@@ -1281,7 +1274,7 @@ void engine<T>::kp_multi(const T *q_host, const T *P, T *RET, int64_t nrhs, int6
             MI_HIP_CHECK(hipMemcpyAsync(lane_v(LV_R, c), RET + (c0 + c) * ld, sizeof(T) * (size_t) m, hipMemcpyHostToDevice, stream));
         }
         int first = 0;
-        if (kcache_tiles > 0 && !kcache_valid) {  // an unfilled tile cache: the first vector fills it, on the single path
+        if (kc.tiles > 0 && !kc.valid) {  // an unfilled tile cache: the first vector fills it, on the single path
             MI_HIP_CHECK(hipMemsetAsync(sc.get(), 0, sizeof(cg_scalars<T>), stream));
             kp_device(lane_v(LV_D, 0), lane_v(LV_R, 0), add, false, nullptr);
             first = 1;
@@ -1357,7 +1350,7 @@ void engine<T>::time_kp_multi(int64_t nrhs, int reps, double *ms_kp) {
 
 template <typename T>
 int64_t engine<T>::device_bytes() const {
-    return XT.bytes() + norms.bytes() + xlast.bytes() + partial.bytes() + kcache.bytes() + kdesc.bytes() + q.bytes() * 10 + w.bytes() +
+    return XT.bytes() + norms.bytes() + xlast.bytes() + partial.bytes() + kc.bytes() + q.bytes() * 10 + w.bytes() +
            csr_bytes() + lanes.bytes();
 }
 

@@ -96,26 +96,39 @@ struct engine : engine_base {
     void tiles_upload();
     // Stored kernel-matrix tiles of the pairwise tile path (kp_tiles.hip, KP_COMPUTE_STORE / KP_LOAD): the values
     // k(x_i, x_j) depend only on the data and the kernel parameters, so the first K·p of a setup that runs without
-    // a stop flag (cg_begin's r0 product, kp_host) stores the first kcache_tiles tiles of this rank's table — all
+    // a stop flag (cg_begin's r0 product, kp_host) stores the first kc.tiles tiles of this rank's table — all
     // of them where mem_budget() allows — and every later K·p streams them instead of recomputing them; the tiles
-    // past the prefix stay implicit. kcache_valid: the records are written (by launches already on the stream).
-    int kp_cache_opt = 0;  // PLSSVM_MI_OPT_KP_CACHE: 0 auto (on where it fits), 1 off; env PLSSVM_MI_KP_CACHE=0: off
-    dev_buf<T> kcache;
-    int64_t kcache_tiles = 0;
-    bool kcache_valid = false;
-    // 7-byte and 53-bit records (kp_pack.hpp, kp_narrow.hpp): one descriptor per cached tile — raw, or the tile's
-    // largest exponent, flagged for the 53-bit form — written by the fill, read by every KP_LOAD workgroup;
-    // kdesc[kcache_tiles] counts the packed tiles of both forms, kdesc[kcache_tiles + 1] the narrow ones. Allocated and
-    // dropped with the cache. fp32 records are never packed.
-    int kp_pack_opt = 0;  // PLSSVM_MI_OPT_KP_PACK: 0 auto (fp64: narrow where eligible, else 7-byte, else raw), 1 off,
-                          // 2 7-byte only; env at setup: PLSSVM_MI_KP_PACK=0 off, PLSSVM_MI_KP_NARROW=0 7-byte only
-    dev_buf<int32_t> kdesc;
-    int kpack_on = 0;             // this setup's fill: 0 every tile raw, 1 raw or 7-byte, 2 all three forms
-    int64_t kpacked_host = -1;    // the counters, read back together on the first request after the fill (-1: not yet)
-    int64_t knarrow_host = 0;
-    int64_t kcache_packed();
-    int64_t kcache_narrow();
-    void kcache_setup();  // after the setup's other allocations
+    // past the prefix stay implicit.
+    struct tile_cache {
+        // the two options outlive a setup; reset() leaves them alone
+        int cache_opt = 0;  // PLSSVM_MI_OPT_KP_CACHE: 0 auto (on where it fits), 1 off; env PLSSVM_MI_KP_CACHE=0: off
+        int pack_opt = 0;   // PLSSVM_MI_OPT_KP_PACK: 0 auto (fp64: narrow where eligible, else wide, else raw), 1 off,
+                            // 2 wide only; env at setup: PLSSVM_MI_KP_PACK=0 off, PLSSVM_MI_KP_NARROW=0 wide only
+        dev_buf<T> rec;
+        int64_t tiles = 0;
+        bool valid = false;  // the records are written (by launches already on the stream)
+        // Packed records (kp_record.hpp): one descriptor per cached tile — raw, or the tile's largest exponent, flagged
+        // for the narrow form — written by the fill, read by every KP_LOAD workgroup; desc[tiles] counts the packed tiles
+        // of both forms, desc[tiles + 1] the narrow ones. Allocated and dropped with the records. fp32 records are
+        // never packed.
+        dev_buf<int32_t> desc;
+        int pack = 0;              // this setup's fill: 0 every tile raw, 1 raw or wide, 2 all three forms
+        int64_t packed_host = -1;  // the counters, read back together on the first request after the fill (-1: not yet)
+        int64_t narrow_host = 0;
+        void reset();
+        void setup(const engine &e);  // after the setup's other allocations
+        int64_t packed(const engine &e);
+        int64_t narrow(const engine &e) { return packed(e) > 0 ? narrow_host : 0; }
+        int64_t bytes() const { return rec.bytes() + desc.bytes(); }
+        // what the launchers see: the first `tiles` records once filled (or while `filling`), else none
+        kp_cache_view<T> view(bool filling = false) const {
+            return { rec.get(), desc.get(), desc.get() + tiles, (valid || filling) ? tiles : 0, pack };
+        }
+    };
+    tile_cache kc;
+    kp_geom<T> kp_geometry() const {
+        return { kf(), XT.get(), norms.get(), n_pad, d_pad, nb, t0, t1 - t0, kp_wgoff.get(), kp_wgs };
+    }
     void kp_tiles_now(const T *p, const cg_scalars<T> *status);  // the tile launches of one K·p
     int64_t r0 = 0, r1 = 0, chunk = 0;    // rows owned by this rank (factored / sparse row paths)
 

@@ -72,29 +72,42 @@ void kp_tile_offsets(int64_t nb, int64_t s0, int64_t nsuper, std::vector<int32_t
 // runs the same epilogue, giving bitwise the computed slab record.
 enum kp_tile_mode { KP_COMPUTE = 0, KP_COMPUTE_STORE = 1, KP_LOAD = 2 };
 constexpr int64_t KP_CACHE_REC = (int64_t) KP_TILE * KP_TILE;
-// tiles [0, cached) from / to kcache (fill: computed and stored, else loaded), tiles [cached, wgs) computed.
-// fp64 records come in three forms (kp_pack.hpp, kp_narrow.hpp): kdesc[tile] says raw (0), or holds the largest
-// exponent E of a tile stored at 7 bytes per value in the first 112 KiB of its record, or E | KP_NARROW_FLAG for a tile
-// stored at 53 bits per value in the first 106 KiB; the fill writes it (pack 0: every tile raw, 1: raw or 7-byte,
-// 2: all three) and adds one to kcount[0] per packed tile of either form and one to kcount[1] per narrow tile, KP_LOAD
-// reads it. Needed whenever cached > 0 in fp64; fp32 ignores it.
+// The rank's tiles: kernel function, data, the super-blocks [s0, s0 + nsuper) and their workgroup table.
 template <typename T>
-void launch_kp_tiles(kfun<T> kf, const T *XT, const T *norms, const T *p, T *partial, int64_t n_pad, int64_t d_pad,
-                     int64_t nb, int64_t s0, int64_t nsuper, const int32_t *wg_off, int64_t wgs,
-                     const cg_scalars<T> *status, hipStream_t s, T *kcache = nullptr, int64_t cached = 0,
-                     bool fill = false, int32_t *kdesc = nullptr, int32_t *kcount = nullptr, int pack = 0);
+struct kp_geom {
+    kfun<T> kf;
+    const T *XT, *norms;
+    int64_t n_pad, d_pad, nb, s0, nsuper;
+    const int32_t *wg_off;
+    int64_t wgs;
+};
+// The tile cache as a launch sees it: tiles [0, cached) have a record in rec. fp64 records come in three forms
+// (kp_record.hpp): desc[tile] says raw (0), or holds the largest exponent E of a wide tile (7 bytes per value, the first
+// 112 KiB of its record), or E | KP_DESC_NARROW for a narrow one (53 bits per value, the first 106 KiB); the fill writes
+// it (pack 0: every tile raw, 1: raw or wide, 2: all three) and adds one to count[0] per packed tile of either form and
+// one to count[1] per narrow tile, KP_LOAD reads it. desc and count are needed whenever cached > 0 in fp64 (the batched
+// launch: desc only); fp32 ignores them.
+template <typename T>
+struct kp_cache_view {
+    T *rec = nullptr;
+    int32_t *desc = nullptr, *count = nullptr;
+    int64_t cached = 0;
+    int pack = 0;
+};
+// tiles [0, cached) from / to the cache (fill: computed and stored, else loaded), tiles [cached, wgs) computed.
+template <typename T>
+void launch_kp_tiles(const kp_geom<T> &g, const T *p, T *partial, const cg_scalars<T> *status, hipStream_t s,
+                     const kp_cache_view<T> &kc = {}, bool fill = false);
 
 // The same tiles for nvec vectors at once (2 .. KP_MULTI_W; 1 is legal): vector c is p + c * pstride, its slab
 // partial + c * sstride, its stop flag status[c] (status null: none; a vector whose flag says converged is skipped and
 // its slab left alone). A tile's kernel values are formed or streamed once per visit and multiplied with every
 // vector in the single-vector kernel's order: slab c is bitwise launch_kp_tiles' slab for p_c. Tiles [0, cached) are
-// streamed from kcache, whose records must be filled (launch_kp_tiles with fill), the rest are computed.
+// streamed from the cache, whose records must be filled (launch_kp_tiles with fill), the rest are computed.
 constexpr int KP_MULTI_W = 8;
 template <typename T>
-void launch_kp_tiles_multi(kfun<T> kf, const T *XT, const T *norms, const T *p, int64_t pstride, T *partial,
-                           int64_t sstride, int nvec, int64_t n_pad, int64_t d_pad, int64_t nb, int64_t s0,
-                           int64_t nsuper, const int32_t *wg_off, int64_t wgs, const cg_scalars<T> *status, hipStream_t s,
-                           const T *kcache = nullptr, int64_t cached = 0, const int32_t *kdesc = nullptr);
+void launch_kp_tiles_multi(const kp_geom<T> &g, const T *p, int64_t pstride, T *partial, int64_t sstride, int nvec,
+                           const cg_scalars<T> *status, hipStream_t s, const kp_cache_view<T> &kc = {});
 
 // ---- fused dense predict tiles (predict_tiles.hip) -------------------------------------------------
 // One workgroup owns a 128-point tile and one segment of PRED_SEG consecutive 128-row support-vector tiles. The

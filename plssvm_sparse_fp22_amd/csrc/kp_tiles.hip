@@ -21,8 +21,7 @@
 
 #include "kernels.hpp"
 #include "kp_device.hpp"
-#include "kp_pack.hpp"
-#include "kp_narrow.hpp"
+#include "kp_record.hpp"
 
 namespace plssvm_mi {
 
@@ -91,12 +90,12 @@ constexpr int KP_OFF_PAN = 4 * KP_TILE;
 constexpr int KP_RSTR = 17, KP_RHALF = KP_TILE * KP_RSTR + 1, KP_CSTR = 5;
 
 // The fp64 KP_LOAD workgroup: the tile's record -> registers -> the "times p" epilogue of kp_tile_kernel (the same
-// fma chains, LDS park and fixed-order sums, so the slab record is bitwise the computed one). FORM: KP_FORM_WIDE, the
-// record is the 7-byte form of kp_pack.hpp — 28 dwordx4 per lane instead of 32, each value's high dword rebuilt from
-// its 24-bit word and the tile's base just before its fma; KP_FORM_NARROW, the 53-bit form of kp_narrow.hpp — 26
-// dwordx4 and one dwordx2 per lane, the high dword rebuilt from its 21-bit word of the lane's bit stream. All of the
-// lane's loads are issued before the first use: the whole record (106, 112 or 128 KiB) is in flight. MULTI: the values
-// are decoded once, then multiplied with every live vector as in kp_tile_kernel's MULTI epilogue.
+// fma chains, LDS park and fixed-order sums, so the slab record is bitwise the computed one). FORM: KP_FORM_WIDE and
+// KP_FORM_NARROW, the record is a packed one of kp_record.hpp with 24-bit or 21-bit fields — 28 dwordx4 per lane, or
+// 26 and one dwordx2, instead of 32, each value's high dword rebuilt from its field of the lane's bit stream and the
+// tile's base just before its fma. All of the lane's loads are issued before the first use: the whole record (106, 112
+// or 128 KiB) is in flight. MULTI: the values are decoded once, then multiplied with every live vector as in
+// kp_tile_kernel's MULTI epilogue.
 constexpr int KP_FORM_RAW = 0, KP_FORM_WIDE = 1, KP_FORM_NARROW = 2;
 template <int FORM, bool MULTI>
 __device__ __forceinline__ void kp_load_f64(const double *__restrict__ kcache, int64_t wg, uint32_t base,
@@ -111,36 +110,30 @@ __device__ __forceinline__ void kp_load_f64(const double *__restrict__ kcache, i
     int c = MULTI ? __builtin_ctz(live) : 0;
     double pnext = p[MULTI ? c * pstride + pidx : pidx];
     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-    constexpr bool PACKED = FORM == KP_FORM_WIDE, NARROW = FORM == KP_FORM_NARROW;
-    u32x4 kq[PACKED ? KP_PACK_GROUPS : 1];
-    f64x2 kld[FORM == KP_FORM_RAW ? 32 : 1];
-    u32x4 nl[NARROW ? 16 : 1], nh[NARROW ? KP_NARROW_HGROUPS - 1 : 1];  // L0 .. L15, H0 .. H9
-    u32x2 nh10 = { 0u, 0u };                                            // H10: stream dwords 40 and 41
-    if constexpr (NARROW) {
-        // record order: L_k, then the H group that row k is the first to need (at most one: kp_narrow_hi_row grows)
-        const uint32_t *rec0 = reinterpret_cast<const uint32_t *>(kcache + wg * KP_CACHE_REC);
-        const u32x4 *rec = reinterpret_cast<const u32x4 *>(rec0) + tid;
+    constexpr bool PACKED = FORM != KP_FORM_RAW;
+    using R = kp_record<FORM == KP_FORM_NARROW ? KP_BITS_NARROW : KP_BITS_WIDE>;
+    constexpr int HFULL = R::HDW / 4;  // dwordx4 groups of the bit stream; a rest of two dwords is the dwordx2 tail
+    f64x2 kld[PACKED ? 1 : 32];
+    u32x4 kl[PACKED ? 16 : 1], kh[PACKED ? HFULL : 1];  // L0 .. L15, the full H groups
+    u32x2 kht = { 0u, 0u };
+    if constexpr (PACKED) {
+        // record order: L_k, then the H group that row k is the first to need (at most one: hi_row grows)
+        const uint32_t *rec = reinterpret_cast<const uint32_t *>(kcache + wg * KP_CACHE_REC);
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
-            nl[k] = KP_LOAD_NT ? __builtin_nontemporal_load(rec + kp_narrow_lo_group(k) * 256) : rec[kp_narrow_lo_group(k) * 256];
+            const u32x4 *lo = reinterpret_cast<const u32x4 *>(rec + R::group_dword(R::lo_group(k), tid));
+            kl[k] = KP_LOAD_NT ? __builtin_nontemporal_load(lo) : *lo;
             if constexpr (!MULTI) __builtin_amdgcn_sched_barrier(0);  // issued in record order: they return in order
 #pragma unroll
-            for (int h = 0; h < KP_NARROW_HGROUPS - 1; ++h) {
-                if (kp_narrow_hi_row(h) == k) {
-                    nh[h] = KP_LOAD_NT ? __builtin_nontemporal_load(rec + kp_narrow_hi_group(h) * 256) : rec[kp_narrow_hi_group(h) * 256];
-                    if constexpr (!MULTI) __builtin_amdgcn_sched_barrier(0);
-                }
+            for (int h = 0; h < R::HGROUPS; ++h) {
+                if (R::hi_row(h) != k) continue;
+                const uint32_t *hi = rec + R::group_dword(R::hi_group(h), tid);
+                const u32x4 *hi4 = reinterpret_cast<const u32x4 *>(hi);
+                const u32x2 *hi2 = reinterpret_cast<const u32x2 *>(hi);
+                if (h < HFULL) kh[h] = KP_LOAD_NT ? __builtin_nontemporal_load(hi4) : *hi4;
+                else kht = KP_LOAD_NT ? __builtin_nontemporal_load(hi2) : *hi2;
+                if constexpr (!MULTI) __builtin_amdgcn_sched_barrier(0);
             }
-        }
-        const u32x2 *rec2 = reinterpret_cast<const u32x2 *>(rec0 + kp_narrow_group_dword(KP_NARROW_GROUPS - 1, 0)) + tid;
-        nh10 = KP_LOAD_NT ? __builtin_nontemporal_load(rec2) : *rec2;
-        if constexpr (!MULTI) __builtin_amdgcn_sched_barrier(0);
-    } else if constexpr (PACKED) {
-        const u32x4 *rec = reinterpret_cast<const u32x4 *>(kcache + wg * KP_CACHE_REC) + tid;
-#pragma unroll
-        for (int g = 0; g < KP_PACK_GROUPS; ++g) {
-            kq[g] = KP_LOAD_NT ? __builtin_nontemporal_load(rec + g * 256) : rec[g * 256];
-            if constexpr (!MULTI) __builtin_amdgcn_sched_barrier(0);  // issued in record order: they return in order
         }
     } else {
         const f64x2 *rec = reinterpret_cast<const f64x2 *>(kcache + wg * KP_CACHE_REC) + tid;
@@ -155,18 +148,12 @@ __device__ __forceinline__ void kp_load_f64(const double *__restrict__ kcache, i
     // (left to itself the scheduler gathers the integer decode of all rows behind the first LDS read: vmcnt(1) at once)
     if constexpr (!MULTI) __builtin_amdgcn_sched_barrier(0);
     // value nt of row (mt, r); every index is a constant once the loops are unrolled
-    auto nword = [&](int j) -> uint32_t { return j < 40 ? nh[j >> 2][j & 3] : nh10[j & 1]; };  // dword j of the bit stream
+    auto kword = [&](int j) -> uint32_t { return j < 4 * HFULL ? kh[j >> 2][j & 3] : kht[j & 1]; };  // dword j of the bit stream
     auto kval = [&](int mt, int r, int nt) -> double {
-        if constexpr (NARROW) {
-            const int v = (mt * 4 + r) * 4 + nt, j = kp_narrow_word(v);
-            const uint32_t hi = kp_narrow_unpack(v, nword(j), nword(kp_narrow_straddles(v) ? j + 1 : j), base);
-            return __hiloint2double((int) hi, (int) nl[mt * 4 + r][nt]);
-        } else if constexpr (PACKED) {
-            const int d0 = 3 * r;
-            const uint32_t lo = kq[kp_pack_lo_group(mt, r)][nt];
-            const uint32_t hi = kp_unpack4(nt, kq[kp_pack_hi_group(mt, d0)][d0 & 3], kq[kp_pack_hi_group(mt, d0 + 1)][(d0 + 1) & 3],
-                                           kq[kp_pack_hi_group(mt, d0 + 2)][(d0 + 2) & 3], base);
-            return __hiloint2double((int) hi, (int) lo);
+        if constexpr (PACKED) {
+            const int v = (mt * 4 + r) * 4 + nt, j = R::word(v);
+            const uint32_t hi = R::unpack(v, kword(j), kword(R::straddles(v) ? j + 1 : j), base);
+            return __hiloint2double((int) hi, (int) kl[mt * 4 + r][nt]);
         } else {
             return kld[((mt * 4 + r) * 4 + nt) / 2][nt & 1];
         }
@@ -278,13 +265,38 @@ __device__ __forceinline__ void kp_load_f64(const double *__restrict__ kcache, i
     }
 }
 
+// The fill's store of row `row` (0 .. 15, a constant once unrolled, and with it every position below) of a lane's packed
+// record at rec: L_row, the row's four fields appended to the lane's bit stream w (carried across the rows; unrolled,
+// every dword is a value of its own that lives from the first field that reaches it to the store of its group), and
+// the H groups this row completed.
+template <int BITS, typename T>
+__device__ __forceinline__ void kp_store_row(uint32_t *rec, int tid, int row, const T *kv, uint32_t base, uint32_t *w) {
+    using R = kp_record<BITS>;
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    u32x4 lo;
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+        lo[nt] = (uint32_t) __double2loint((double) kv[nt]);
+        R::put(row * 4 + nt, (uint32_t) __double2hiint((double) kv[nt]) - base, w);
+    }
+    *reinterpret_cast<u32x4 *>(rec + R::group_dword(R::lo_group(row), tid)) = lo;
+#pragma unroll
+    for (int h = 0; h < R::HGROUPS; ++h) {
+        if (h >= R::hi_done(row) || (row > 0 && h < R::hi_done(row - 1))) continue;
+        uint32_t *at = rec + R::group_dword(R::hi_group(h), tid);
+        if (h < R::HDW / 4) *reinterpret_cast<u32x4 *>(at) = u32x4{ w[4 * h], w[4 * h + 1], w[4 * h + 2], w[4 * h + 3] };
+        else *reinterpret_cast<u32x2 *>(at) = u32x2{ w[4 * h], w[4 * h + 1] };
+    }
+}
+
 // MODE (kernels.hpp): KP_COMPUTE forms the tile's kernel values from the data; KP_COMPUTE_STORE also writes them
 // to the tile's cache record kcache[wg]; KP_LOAD reads them from there and runs the same epilogue from "times p_j"
 // on — the same fma order, LDS park and sums, so the slab record is bitwise the computed one. A cache record is
 // in register layout, [value group][thread][VEC]: a lane's 64 values in (mt, r, nt) order, 16 bytes per lane and
 // group, so every wave-instruction moves one contiguous KiB. wg_base: the first workgroup (tile) of this launch.
-// fp64 records come raw, in the 7-byte form of kp_pack.hpp or in the 53-bit form of kp_narrow.hpp, per tile (kdesc[wg]:
-// 0 = raw, the tile's largest exponent E = 7-byte, E | KP_NARROW_FLAG = narrow): the fp64 KP_COMPUTE_STORE instance
+// fp64 records come raw or in one of the two packed forms of kp_record.hpp (wide: 7 bytes per value, narrow: 53 bits),
+// per tile (kdesc[wg]: 0 = raw, the tile's largest exponent E = wide, E | KP_DESC_NARROW = narrow): the fp64 KP_COMPUTE_STORE instance
 // finds the tile's exponent range, writes the descriptor, counts the packed tiles of both forms in kcount[0] and the
 // narrow ones in kcount[1] (pack = 0: every tile raw, 1: no narrow tile) and stores the form; the fp64 KP_LOAD
 // instance is kp_load_f64 above, so the KP_LOAD statements in this body serve fp32 only. fp32 records are always raw.
@@ -344,10 +356,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_wav
     // range made the last rank of 8 3.9 % slower than the others)
     // (KP_LOAD has no panels to keep in an L2: its workgroups walk the records in order)
     const int64_t wg = wg_base + (MODE == KP_LOAD ? (int64_t) blockIdx.x : xcd_remap(blockIdx.x, gridDim.x));
-    // fp64 records may be in the 7-byte form (kp_pack.hpp): the tile's descriptor, one wave-uniform load issued
+    // fp64 records may be in a packed form (kp_record.hpp): the tile's descriptor, one wave-uniform load issued
     // ahead of the table search below so that its latency hides there
     constexpr bool PACK_LOAD = MODE == KP_LOAD && sizeof(T) == 8, PACK_STORE = MODE == KP_COMPUTE_STORE && sizeof(T) == 8;
-    uint32_t desc = KP_PACK_RAW;
+    uint32_t desc = KP_DESC_RAW;
     if constexpr (PACK_LOAD) desc = (uint32_t) kdesc[wg];
     int lo = 0, hi = (int) nsuper;  // largest k with wg_off[k] <= wg
     while (hi - lo > 1) {
@@ -379,11 +391,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_wav
     const int64_t pidx = (tid < KP_TILE) ? I0 + tid : J0 + (tid - KP_TILE);
     if constexpr (PACK_LOAD) {
         if (kp_desc_is_narrow(desc))
-            kp_load_f64<KP_FORM_NARROW, MULTI>(kcache, wg, kp_narrow_base(kp_desc_exp(desc)), p, partial, smem, tid, lane, wr, wc,
-                                               diag, pidx, live, pstride, sstride);
-        else if (desc != KP_PACK_RAW)
-            kp_load_f64<KP_FORM_WIDE, MULTI>(kcache, wg, kp_pack_base(desc), p, partial, smem, tid, lane, wr, wc, diag, pidx, live,
-                                             pstride, sstride);
+            kp_load_f64<KP_FORM_NARROW, MULTI>(kcache, wg, kp_record<KP_BITS_NARROW>::base(kp_desc_exp(desc)), p, partial, smem, tid,
+                                               lane, wr, wc, diag, pidx, live, pstride, sstride);
+        else if (desc != KP_DESC_RAW)
+            kp_load_f64<KP_FORM_WIDE, MULTI>(kcache, wg, kp_record<KP_BITS_WIDE>::base(desc), p, partial, smem, tid, lane, wr, wc, diag,
+                                             pidx, live, pstride, sstride);
         else
             kp_load_f64<KP_FORM_RAW, MULTI>(kcache, wg, 0u, p, partial, smem, tid, lane, wr, wc, diag, pidx, live, pstride,
                                             sstride);
@@ -494,7 +506,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_wav
         // row-half waves). They are parked in LDS and every thread then sums one half-row and one
         // half-column: ~20 adds per lane instead of a 4-level shuffle tree per row (64 adds + 128
         // ds_bpermute); the fixed summation order keeps K·p bitwise reproducible.
-        uint32_t pk_desc = KP_PACK_RAW;  // fp64 KP_COMPUTE_STORE: the tile's descriptor, uniform in the workgroup
+        uint32_t pk_desc = KP_DESC_RAW;  // fp64 KP_COMPUTE_STORE: the tile's descriptor, uniform in the workgroup
         if constexpr (PACK_STORE) {
             // The kernel function once, in place (the call and its arguments are those of the loop below, as in the
             // MULTI branch: the values are bitwise the same), tracking the range of the lane's high dwords; the four
@@ -529,24 +541,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_wav
             __syncthreads();  // every wave is done with the last K chunk: the panels become reduction buffers
             mn = min(min(pk_red[0], pk_red[2]), min(pk_red[4], pk_red[6]));
             mx = max(max(pk_red[1], pk_red[3]), max(pk_red[5], pk_red[7]));
-            pk_desc = __builtin_amdgcn_readfirstlane(pack >= 2 ? kp_narrow_desc(mn, mx) : pack ? kp_pack_desc(mn, mx) : KP_PACK_RAW);
+            pk_desc = __builtin_amdgcn_readfirstlane(kp_desc(mn, mx, pack));
             if (tid == 0) {
                 kdesc[wg] = (int32_t) pk_desc;
-                if (pk_desc != KP_PACK_RAW) atomicAdd(kcount, 1);            // one per packed tile, either form
+                if (pk_desc != KP_DESC_RAW) atomicAdd(kcount, 1);            // one per packed tile, either form
                 if (kp_desc_is_narrow(pk_desc)) atomicAdd(kcount + 1, 1);  // one per narrow tile
             }
         } else {
             __syncthreads();  // every wave is done with the last K chunk: the panels become reduction buffers
         }
         const bool pk_narrow = kp_desc_is_narrow(pk_desc);  // uniform
-        const uint32_t pk_base = pk_narrow ? kp_narrow_base(kp_desc_exp(pk_desc)) : kp_pack_base(pk_desc);
-        // narrow form: the lane's bit stream of 21-bit words, carried across the rows; unrolled, every dword is a value
-        // of its own that lives from the first word that reaches it to the store of its group
-        uint32_t pk_nw[PACK_STORE ? KP_NARROW_HDW : 1];
+        const uint32_t pk_base = pk_narrow ? kp_record<KP_BITS_NARROW>::base(kp_desc_exp(pk_desc)) : kp_record<KP_BITS_WIDE>::base(pk_desc);
+        uint32_t pk_w[PACK_STORE ? kp_record<KP_BITS_WIDE>::HDW : 1];  // the lane's bit stream of either width (kp_store_row)
         T *rowp = smem + OFF_PAN + wc * RHALF;
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
-            uint32_t pk_hw[PACK_STORE ? 12 : 1];  // the mt's 24-bit words: row r in dwords 3r .. 3r + 2
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int il = wr * 64 + mt * 16 + M::row(lane, r);
@@ -571,46 +580,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_wav
                     cs[nt] = fma(kv, pi, cs[nt]);
                 }
                 rowp[il * RSTR + (lane & 15)] = s;
-                if constexpr (PACK_STORE) {
-                    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-                    if (pk_narrow) {
-                        uint32_t *rec0 = reinterpret_cast<uint32_t *>(kcache + wg * KP_CACHE_REC);
-                        const int row = mt * 4 + r;  // a constant once unrolled, and with it every position below
-                        u32x4 lo;
-#pragma unroll
-                        for (int nt = 0; nt < 4; ++nt) {
-                            lo[nt] = (uint32_t) __double2loint((double) kvs[nt]);
-                            kp_narrow_put(row * 4 + nt, kp_narrow_h21((uint32_t) __double2hiint((double) kvs[nt]), pk_base), pk_nw);
-                        }
-                        *reinterpret_cast<u32x4 *>(rec0 + kp_narrow_group_dword(kp_narrow_lo_group(row), tid)) = lo;
-#pragma unroll
-                        for (int h = 0; h < KP_NARROW_HGROUPS; ++h) {  // the groups this row completed
-                            if (h < kp_narrow_hi_done(row) && (row == 0 || h >= kp_narrow_hi_done(row - 1))) {
-                                uint32_t *at = rec0 + kp_narrow_group_dword(kp_narrow_hi_group(h), tid);
-                                if (h < KP_NARROW_HGROUPS - 1) {
-                                    *reinterpret_cast<u32x4 *>(at) = u32x4{ pk_nw[4 * h], pk_nw[4 * h + 1], pk_nw[4 * h + 2], pk_nw[4 * h + 3] };
-                                } else {
-                                    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-                                    *reinterpret_cast<u32x2 *>(at) = u32x2{ pk_nw[4 * h], pk_nw[4 * h + 1] };
-                                }
-                            }
-                        }
-                    } else if (pk_desc != KP_PACK_RAW) {  // uniform
-                        u32x4 *rec = reinterpret_cast<u32x4 *>(kcache + wg * KP_CACHE_REC) + tid;
-                        uint32_t hi[4];
-                        u32x4 lo;
-#pragma unroll
-                        for (int nt = 0; nt < 4; ++nt) {
-                            lo[nt] = (uint32_t) __double2loint((double) kvs[nt]);
-                            hi[nt] = (uint32_t) __double2hiint((double) kvs[nt]);
-                        }
-                        kp_pack4(hi, pk_base, pk_hw + 3 * r);
-                        rec[kp_pack_lo_group(mt, r) * 256] = lo;
-                        if (r >= 1) {  // dwords 4 (r - 1) .. 4 (r - 1) + 3 are complete
-                            const int d = 4 * (r - 1);
-                            rec[kp_pack_hi_group(mt, d) * 256] = u32x4{ pk_hw[d], pk_hw[d + 1], pk_hw[d + 2], pk_hw[d + 3] };
-                        }
-                    } else {
+                if constexpr (MODE == KP_COMPUTE_STORE) {
+                    bool raw = true;  // uniform, like the two tests below
+                    if constexpr (PACK_STORE) {
+                        uint32_t *rec = reinterpret_cast<uint32_t *>(kcache + wg * KP_CACHE_REC);
+                        raw = pk_desc == KP_DESC_RAW;
+                        if (pk_narrow) kp_store_row<KP_BITS_NARROW>(rec, tid, mt * 4 + r, kvs, pk_base, pk_w);
+                        else if (!raw) kp_store_row<KP_BITS_WIDE>(rec, tid, mt * 4 + r, kvs, pk_base, pk_w);
+                    }
+                    if (raw) {
                         vec_t *rec = reinterpret_cast<vec_t *>(kcache + wg * KP_CACHE_REC) + tid;
 #pragma unroll
                         for (int h = 0; h < 4 / VEC; ++h) {
@@ -619,15 +597,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_wav
                             for (int e = 0; e < VEC; ++e) v[e] = kvs[h * VEC + e];
                             rec[((mt * 4 + r) * (4 / VEC) + h) * 256] = v;
                         }
-                    }
-                } else if constexpr (MODE == KP_COMPUTE_STORE) {
-                    vec_t *rec = reinterpret_cast<vec_t *>(kcache + wg * KP_CACHE_REC) + tid;
-#pragma unroll
-                    for (int h = 0; h < 4 / VEC; ++h) {
-                        vec_t v;
-#pragma unroll
-                        for (int e = 0; e < VEC; ++e) v[e] = kvs[h * VEC + e];
-                        rec[((mt * 4 + r) * (4 / VEC) + h) * 256] = v;
                     }
                 }
             }
@@ -810,18 +779,18 @@ namespace {
 
 // one launch of `count` workgroups (tiles [base, base + count) of the rank's table) in one mode
 template <typename T, int MODE>
-void launch_kp_mode(kfun<T> kf, const T *XT, const T *norms, const T *p, T *partial, int64_t n_pad, int64_t d_pad,
-                    int64_t nb, int64_t s0, int64_t nsuper, const int32_t *wg_off, int64_t base, int64_t count,
-                    const cg_scalars<T> *status, T *kcache, int32_t *kdesc, int32_t *kcount, int pack, hipStream_t s) {
+void launch_kp_mode(const kp_geom<T> &g, const T *p, T *partial, int64_t base, int64_t count, const cg_scalars<T> *status,
+                    const kp_cache_view<T> &kc, hipStream_t s) {
     if (count <= 0) return;
     const dim3 grid((unsigned) count), block(256);
-#define KP_LAUNCH(KERNEL)                                                                                         \
-    hipLaunchKernelGGL((kp_tile_kernel<T, KERNEL, MODE>), grid, block, 0, s, kf, XT, norms, p, partial, n_pad, d_pad, \
-                       nb, s0, nsuper, wg_off, status, base, kcache, 1, (int64_t) 0, (int64_t) 0, kdesc, kcount, pack)
+#define KP_LAUNCH(KERNEL)                                                                                               \
+    hipLaunchKernelGGL((kp_tile_kernel<T, KERNEL, MODE>), grid, block, 0, s, g.kf, g.XT, g.norms, p, partial, g.n_pad,    \
+                       g.d_pad, g.nb, g.s0, g.nsuper, g.wg_off, status, base, kc.rec, 1, (int64_t) 0, (int64_t) 0, kc.desc, \
+                       kc.count, kc.pack)
     if constexpr (MODE == KP_LOAD) {
         KP_LAUNCH(0);  // one instance per real type: the stored values are past the kernel function
     } else {
-        switch (kf.kernel) {
+        switch (g.kf.kernel) {
             case 0: KP_LAUNCH(0); break;
             case 1: KP_LAUNCH(1); break;
             default: KP_LAUNCH(2); break;
@@ -831,63 +800,56 @@ void launch_kp_mode(kfun<T> kf, const T *XT, const T *norms, const T *p, T *part
     MI_LAUNCH_CHECK();
 }
 
+// what both launchers check first; returns the cached prefix of the rank's tiles that the launch may use
+template <typename T>
+int64_t kp_cached_prefix(const kp_geom<T> &g, const kp_cache_view<T> &kc, bool need_count) {
+    // 32-bit DMA offsets inside a chunk (kp_tile_kernel): (BK - 1) rows of n_pad plus a tile row
+    if ((int64_t) kp_dpad<T>() * g.n_pad * (int64_t) sizeof(T) >= ((int64_t) 1 << 31))
+        throw mi_error(-5, "too many points for the pairwise tile kernel's 32-bit chunk offsets");
+    const int64_t cached = (kc.rec == nullptr || kc.cached < 0) ? 0 : (kc.cached > g.wgs ? g.wgs : kc.cached);
+    if (cached > 0 && sizeof(T) == 8 && (kc.desc == nullptr || (need_count && kc.count == nullptr)))
+        throw mi_error(-1, "fp64 tile records need their descriptors");
+    return cached;
+}
+
 }  // namespace
 
-// Tiles [0, cached) of the rank's table have a record in kcache: they are streamed from it (KP_LOAD), or, with
+// Tiles [0, cached) of the rank's table have a record in the cache: they are streamed from it (KP_LOAD), or, with
 // `fill`, computed and stored (KP_COMPUTE_STORE); tiles [cached, wgs) are computed. cached = 0: one KP_COMPUTE
 // launch over all tiles. Every mode writes the same slab records, so the split never shows in K·p.
 template <typename T>
-void launch_kp_tiles(kfun<T> kf, const T *XT, const T *norms, const T *p, T *partial, int64_t n_pad, int64_t d_pad,
-                     int64_t nb, int64_t s0, int64_t nsuper, const int32_t *wg_off, int64_t wgs,
-                     const cg_scalars<T> *status, hipStream_t s, T *kcache, int64_t cached, bool fill, int32_t *kdesc,
-                     int32_t *kcount, int pack) {
-    if (nsuper <= 0 || nb <= 0 || wgs <= 0) return;
-    // 32-bit DMA offsets inside a chunk (kp_tile_kernel): (BK - 1) rows of n_pad plus a tile row
-    if ((int64_t) kp_dpad<T>() * n_pad * (int64_t) sizeof(T) >= ((int64_t) 1 << 31))
-        throw mi_error(-5, "too many points for the pairwise tile kernel's 32-bit chunk offsets");
-    if (kcache == nullptr || cached < 0) cached = 0;
-    if (cached > wgs) cached = wgs;
-    if (cached > 0 && sizeof(T) == 8 && (kdesc == nullptr || kcount == nullptr))
-        throw mi_error(-1, "fp64 tile records need their descriptors");
-    if (fill)
-        launch_kp_mode<T, KP_COMPUTE_STORE>(kf, XT, norms, p, partial, n_pad, d_pad, nb, s0, nsuper, wg_off, 0, cached,
-                                            status, kcache, kdesc, kcount, pack, s);
-    else
-        launch_kp_mode<T, KP_LOAD>(kf, XT, norms, p, partial, n_pad, d_pad, nb, s0, nsuper, wg_off, 0, cached, status,
-                                   kcache, kdesc, kcount, 0, s);
-    launch_kp_mode<T, KP_COMPUTE>(kf, XT, norms, p, partial, n_pad, d_pad, nb, s0, nsuper, wg_off, cached, wgs - cached,
-                                  status, nullptr, nullptr, nullptr, 0, s);
+void launch_kp_tiles(const kp_geom<T> &g, const T *p, T *partial, const cg_scalars<T> *status, hipStream_t s,
+                     const kp_cache_view<T> &kc, bool fill) {
+    if (g.nsuper <= 0 || g.nb <= 0 || g.wgs <= 0) return;
+    const int64_t cached = kp_cached_prefix(g, kc, true);
+    if (fill) launch_kp_mode<T, KP_COMPUTE_STORE>(g, p, partial, 0, cached, status, kc, s);
+    else launch_kp_mode<T, KP_LOAD>(g, p, partial, 0, cached, status, kc, s);
+    launch_kp_mode<T, KP_COMPUTE>(g, p, partial, cached, g.wgs - cached, status, {}, s);
 }
 
 // The batched form: nvec vectors p + c * pstride into the slabs partial + c * sstride, stop flags status[c] (null:
 // none). The cached prefix must be filled already (the single-vector path's first K·p does that): tiles [0, cached)
 // are streamed, the rest computed, each once for all vectors.
 template <typename T>
-void launch_kp_tiles_multi(kfun<T> kf, const T *XT, const T *norms, const T *p, int64_t pstride, T *partial,
-                           int64_t sstride, int nvec, int64_t n_pad, int64_t d_pad, int64_t nb, int64_t s0,
-                           int64_t nsuper, const int32_t *wg_off, int64_t wgs, const cg_scalars<T> *status, hipStream_t s,
-                           const T *kcache, int64_t cached, const int32_t *kdesc) {
-    if (nsuper <= 0 || nb <= 0 || wgs <= 0) return;
+void launch_kp_tiles_multi(const kp_geom<T> &g, const T *p, int64_t pstride, T *partial, int64_t sstride, int nvec,
+                           const cg_scalars<T> *status, hipStream_t s, const kp_cache_view<T> &kc) {
+    if (g.nsuper <= 0 || g.nb <= 0 || g.wgs <= 0) return;
     if (nvec < 1 || nvec > KP_MULTI_W) throw mi_error(-1, "bad vector count for the batched tile kernel");
-    if ((int64_t) kp_dpad<T>() * n_pad * (int64_t) sizeof(T) >= ((int64_t) 1 << 31))
-        throw mi_error(-5, "too many points for the pairwise tile kernel's 32-bit chunk offsets");
-    if (kcache == nullptr || cached < 0) cached = 0;
-    if (cached > wgs) cached = wgs;
-    if (cached > 0 && sizeof(T) == 8 && kdesc == nullptr) throw mi_error(-1, "fp64 tile records need their descriptors");
+    const int64_t cached = kp_cached_prefix(g, kc, false);
     const dim3 block(256);
-#define KP_LAUNCH(KERNEL, MODE, base, count)                                                                          \
-    hipLaunchKernelGGL((kp_tile_kernel<T, KERNEL, MODE, true>), dim3((unsigned) (count)), block, 0, s, kf, XT, norms, p, \
-                       partial, n_pad, d_pad, nb, s0, nsuper, wg_off, status, (int64_t) (base), const_cast<T *>(kcache),  \
-                       nvec, pstride, sstride, const_cast<int32_t *>(kdesc), (int32_t *) nullptr, 0)
+#define KP_LAUNCH(KERNEL, MODE, base, count)                                                                               \
+    hipLaunchKernelGGL((kp_tile_kernel<T, KERNEL, MODE, true>), dim3((unsigned) (count)), block, 0, s, g.kf, g.XT, g.norms, p, \
+                       partial, g.n_pad, g.d_pad, g.nb, g.s0, g.nsuper, g.wg_off, status, (int64_t) (base), kc.rec, nvec,      \
+                       pstride, sstride, kc.desc, (int32_t *) nullptr, 0)
     if (cached > 0) {
         KP_LAUNCH(0, KP_LOAD, 0, cached);
         MI_LAUNCH_CHECK();
     }
-    if (wgs > cached) {
-        switch (kf.kernel) {
-            case 0: KP_LAUNCH(0, KP_COMPUTE, cached, wgs - cached); break;
-            case 1: KP_LAUNCH(1, KP_COMPUTE, cached, wgs - cached); break;
-            default: KP_LAUNCH(2, KP_COMPUTE, cached, wgs - cached); break;
+    if (g.wgs > cached) {
+        switch (g.kf.kernel) {
+            case 0: KP_LAUNCH(0, KP_COMPUTE, cached, g.wgs - cached); break;
+            case 1: KP_LAUNCH(1, KP_COMPUTE, cached, g.wgs - cached); break;
+            default: KP_LAUNCH(2, KP_COMPUTE, cached, g.wgs - cached); break;
         }
         MI_LAUNCH_CHECK();
     }
@@ -906,15 +868,12 @@ void launch_kp_reduce(const T *partial, int64_t nb, int64_t m, int64_t s0, int64
     MI_LAUNCH_CHECK();
 }
 
-#define INST(T)                                                                                                  \
-    template void launch_kp_tiles<T>(kfun<T>, const T *, const T *, const T *, T *, int64_t, int64_t, int64_t, \
-                                     int64_t, int64_t, const int32_t *, int64_t, const cg_scalars<T> *,        \
-                                     hipStream_t, T *, int64_t, bool, int32_t *, int32_t *, int);      \
-    template void launch_kp_tiles_multi<T>(kfun<T>, const T *, const T *, const T *, int64_t, T *, int64_t, int,  \
-                                           int64_t, int64_t, int64_t, int64_t, int64_t, const int32_t *, int64_t,  \
-                                           const cg_scalars<T> *, hipStream_t, const T *, int64_t,     \
-                                           const int32_t *);                                                      \
-    template void launch_kp_reduce<T>(const T *, int64_t, int64_t, int64_t, int64_t, const int32_t *, T *,     \
+#define INST(T)                                                                                                     \
+    template void launch_kp_tiles<T>(const kp_geom<T> &, const T *, T *, const cg_scalars<T> *, hipStream_t,       \
+                                     const kp_cache_view<T> &, bool);                                                \
+    template void launch_kp_tiles_multi<T>(const kp_geom<T> &, const T *, int64_t, T *, int64_t, int,              \
+                                           const cg_scalars<T> *, hipStream_t, const kp_cache_view<T> &);            \
+    template void launch_kp_reduce<T>(const T *, int64_t, int64_t, int64_t, int64_t, const int32_t *, T *,         \
                                       const cg_scalars<T> *, hipStream_t);
 INST(float)
 INST(double)

@@ -1385,7 +1385,7 @@ void engine<T>::setup_sparse_dense() {
     MI_LAUNCH_CHECK();
     MI_HIP_CHECK(hipStreamSynchronize(stream));
     csr.dense_on = true;
-    kcache_setup();
+    kc.setup(*this);
 }
 
 template <typename T>

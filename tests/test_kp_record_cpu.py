@@ -1,0 +1,49 @@
+"""The packed record formats of stored fp64 tiles (csrc/kp_record.hpp) on the CPU.
+
+The format is plain integer functions shared by the store kernel, the load kernel and tests/kp_record_check.cpp; this
+test builds that program with the host compiler and runs it: classification of tiles (raw / wide / narrow), the two
+stored layouts restated as literals, bit-exact round trips of whole lane records through the record order at both field
+widths, and the groups a row reads. A second build runs under the address and undefined-behaviour sanitizers, as a
+plain executable.
+"""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "kp_record_check.cpp")
+INC = os.path.join(ROOT, "plssvm_sparse_fp22_amd", "csrc")
+SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+
+
+def _cxx():
+    cxx = shutil.which(os.environ.get("CXX", "c++")) or shutil.which("g++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.fail("no host C++ compiler found")
+    return cxx
+
+
+def _build_and_run(exe, flags):
+    subprocess.run([_cxx(), "-std=c++17", "-O1", "-g", "-Wall", "-Werror", *flags, "-I", INC, SRC, "-o", str(exe)], check=True)
+    run = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert run.stdout.strip().endswith("ok"), run.stdout
+
+
+def test_kp_record_format(tmp_path):
+    _build_and_run(tmp_path / "kp_record_check", [])
+
+
+def _has_sanitizer_runtime(tmp_path):
+    probe = tmp_path / "probe.cpp"
+    probe.write_text("int main() { return 0; }\n")
+    r = subprocess.run([_cxx(), *SANITIZE, str(probe), "-o", str(tmp_path / "probe")], capture_output=True, text=True)
+    return r.returncode == 0 and subprocess.run([str(tmp_path / "probe")]).returncode == 0
+
+
+def test_kp_record_format_under_sanitizers(tmp_path):
+    if not _has_sanitizer_runtime(tmp_path):
+        pytest.skip("the host compiler has no address / undefined-behaviour sanitizer runtime")
+    _build_and_run(tmp_path / "kp_record_check_san", SANITIZE)
