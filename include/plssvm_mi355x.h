@@ -381,7 +381,7 @@ typedef struct {
     int exp_waves;      /* kernel expansion: waves of the remainder stream */
     int64_t exp_chunks; /* kernel expansion: 4-slot chunks of the remainder stream (this rank's rows); 0 = run layout */
     int exp_hbytes;     /* kernel expansion: bytes of a stored remainder value (2 = bfloat16 under the precision
-                           bound of expand.hip "H storage", else sizeof(real)) */
+                           bound of expand_setup.hip "H storage", else sizeof(real)) */
     int exp_layout;     /* kernel expansion: remainder stream layout — 1 = 4-slot chunks with a stored row index per
                            chunk, 2 = 4-slot chunks whose rows are numbered by row-start flags (no row index),
                            4 = row-start flags per slot pair (cells padded to 2 slots); 0 = no expansion

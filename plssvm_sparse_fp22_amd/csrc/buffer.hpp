@@ -46,4 +46,17 @@ class dev_buf {
     int64_t n_ = 0;
 };
 
+// n values of device memory on the host, after everything queued on the stream before them: synchronises
+template <typename V>
+void read_back(V *host, const V *dev, int64_t n, hipStream_t s) {
+    if (n > 0) MI_HIP_CHECK(hipMemcpyAsync(host, dev, sizeof(V) * (size_t) n, hipMemcpyDeviceToHost, s));
+    MI_HIP_CHECK(hipStreamSynchronize(s));
+}
+template <typename V>
+V read_back(const V *dev, hipStream_t s) {
+    V v{};
+    read_back(&v, dev, 1, s);
+    return v;
+}
+
 }  // namespace plssvm_mi

@@ -11,6 +11,7 @@
 #include <vector>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 
@@ -42,6 +43,16 @@ inline int exception_code(const std::exception &e) {
     } while (0)
 
 #define MI_LAUNCH_CHECK() MI_HIP_CHECK(hipGetLastError())
+
+// environment knobs: NAME is set to exactly VALUE; NAME as an integer (0 when unset or not a number)
+inline bool env_is(const char *name, const char *value) {
+    const char *e = std::getenv(name);
+    return e != nullptr && std::strcmp(e, value) == 0;
+}
+inline long long env_long(const char *name) {
+    const char *e = std::getenv(name);
+    return e != nullptr ? std::atoll(e) : 0;
+}
 
 // setup phase timer: PLSSVM_MI_TIMING=1 prints "[plssvm_mi] <phase> <seconds>" to stderr (measurements)
 struct phase_timer {

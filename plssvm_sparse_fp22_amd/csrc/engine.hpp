@@ -38,7 +38,7 @@ inline ncclDataType_t nccl_type() {
     } while (0)
 
 int exp_dot2_built();  // expand.hip: 1 if the bfloat16 remainder's dot-instruction kernel was compiled (EXP_DOT2)
-void exp_load_code_object();  // expand.hip: its code object loaded (one kernel's attributes queried)
+void exp_load_code_object();  // expand.hip and expand_setup.hip: their code objects loaded (a kernel's attributes queried)
 void partition_superblocks(int64_t nb, int rank, int world, int64_t &s0, int64_t &s1, int64_t &s_total,
                            int64_t &tiles_total, int64_t &tiles_local);
 
@@ -362,7 +362,7 @@ struct engine : engine_base {
     void otf_dominant(const T *p, const cg_scalars<T> *status);
     void otf_kp_raw(const T *p, const cg_scalars<T> *status, bool with_base);
     bool sparse_stored() const { return sparse && !csr.dense_on; } // K·p through the CSR structures
-    bool expansion_eligible();                                    // expand.hip: K, coefficients; true if usable
+    bool expansion_eligible();                                    // expand_setup.hip: K, coefficients; true if usable
     // multi-overlap remainder H, diagonal; before_agree (optional): waits for a step the caller runs concurrently
     // (the SELL plans, on a host thread) and returns its failure, which joins the group's agreement and is rethrown
     void build_expansion(const int64_t *cpos, int64_t max_inc,

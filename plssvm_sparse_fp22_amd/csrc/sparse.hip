@@ -776,9 +776,9 @@ void engine<T>::setup_csr(const int64_t *rowptr, const int32_t *col, const void 
     if (!val && rowptr[n_] > 0) throw mi_error(-1, "CSR values missing");
     if (val_fmt != PLSSVM_MI_VAL_REAL && val_fmt != PLSSVM_MI_VAL_FP22) throw mi_error(-1, "unknown value format");
     if (val_fmt == PLSSVM_MI_VAL_FP22 && sizeof(T) != 4) throw mi_error(-5, "FP22 values need a float context");
-    // HIP loads expand.hip's code object (11 MB of device code) at the first launch of one of its kernels, ~0.1 s into
-    // the expansion's build on the critical path of a process's first sparse setup: for the kernels that can use the
-    // expansion (poly, rbf) a host thread loads it now, once per process, beside the uploads and the CSC sort
+    // HIP loads the code objects of expand.hip and expand_setup.hip (11 MB of device code) at the first launch of one
+    // of their kernels, ~0.1 s into the expansion's build on the critical path of a process's first sparse setup: for the
+    // kernels that can use the expansion (poly, rbf) a host thread loads them now, once per process, beside the uploads and the CSC sort
     // (sparse.hip kernels); it is joined before the expansion is built (and at the latest when setup_csr returns)
     struct loader_t {
         std::thread t;

@@ -5,6 +5,7 @@
 #pragma once
 
 #include "buffer.hpp"
+#include "exp_geometry.hpp"
 #include "fp22.hpp"
 #include "kernels.hpp"
 #include "spmv.hpp"
@@ -27,29 +28,21 @@ struct gram_cell {
     double smax;     // max |s_ij| over the cell's pairs (setup: the factored rbf form and its small-argument polynomial)
 };
 
-// ---- kernel expansion path (sparse poly / rbf), see DESIGN.md §5 and expand.hip ----------------------
+// ---- kernel expansion path (sparse poly / rbf), see DESIGN.md §5, expand.hip and expand_setup.hip ----------------------
 // sum_j k_ij p_j = base_i + scale_i * sum_j [ sum_{f shared by i, j} phi(x_if x_jf) + H_ij ] w_j
 // with phi a polynomial of degree K (exact for poly, Taylor for the factored rbf), evaluated per
 // feature through the column moments M_k(f) = sum_{j in col f} x_jf^k w_j, and H_ij the remainder of
 // the pairs sharing two or more features (stored, symmetric, rows padded to 8 slots).
 constexpr int EXP_KMAX = 16;
-constexpr int EXP_NWV = 16;  // waves per remainder-stream workgroup (one workgroup per CU)
-// Remainder-stream geometry: one 1024-thread workgroup per block of RB rows (RB / EXP_NWV rows per
-// wave) holds an LDS row accumulator (RB values) and one LDS window of CW partners (the next window is
-// prefetched into registers), together the CU's 160 KiB. RBB = accumulator bytes in {4, 8, 16, 32} KiB;
-// setup picks the largest whose block count still fills the CUs (bigger blocks = w restaged fewer
-// times; a bigger window = fewer (row, window) groups = less 4-slot padding).
-constexpr int EXP_LDS = 163840;
+// EXP_NWV, EXP_LDS and the host's geometry choice: exp_geometry.hpp
 template <typename T, int RBB>
 constexpr int exp_rb_of() { return RBB / (int) sizeof(T); }
 template <typename T, int RBB>
 constexpr int exp_cw_of() { return (EXP_LDS - RBB) / (int) sizeof(T) / 1024 * 1024; }
-inline int exp_cw_host(int rbb, int es) { return (EXP_LDS - rbb) / es / 1024 * 1024; }
-// bfloat16 windows (hbf16, expand.hip "H storage"): twice the partners in the same LDS, at most 65536
+// bfloat16 windows (hbf16, expand_setup.hip "H storage"): twice the partners in the same LDS, at most 65536
 // (16-bit window-local j)
 template <int RBB>
 constexpr int exp_cw16_of() { return (EXP_LDS - RBB) / 2 / 1024 * 1024 < 65536 ? (EXP_LDS - RBB) / 2 / 1024 * 1024 : 65536; }
-inline int exp_cw16_host(int rbb) { return std::min((EXP_LDS - rbb) / 2 / 1024 * 1024, 65536); }
 
 // phi's polynomial coefficients (kernel argument of the moment / Horner kernels)
 struct coefs {
@@ -78,7 +71,7 @@ struct exp_data {
     dev_buf<T> hslab;                  // [G][rows] partial row sums of the window groups
     dev_buf<uint16_t> hjl;            // [slots] j - W * CW
     dev_buf<T> hv;                    // [slots] H_ij (the real type)
-    dev_buf<uint16_t> hv16;           // [slots] H_ij as bfloat16 (hbf16: see expand.hip, "H storage")
+    dev_buf<uint16_t> hv16;           // [slots] H_ij as bfloat16 (hbf16: see expand_setup.hip, "H storage")
     dev_buf<uint16_t> wv16;           // [m] the stream's partner weights w_j as bfloat16 (hbf16)
     bool hbf16 = false;
     bool dot2 = true;                 // bfloat16 H: the dot-instruction kernel (PLSSVM_MI_EXP_DOT2=0: the FMA chain)

@@ -120,7 +120,7 @@ def remainder_reference(rowptr, col, val, n, d, rows, kernel, gamma, p, coef0=0.
     return want, scale
 
 
-# the remainder's tolerance relative to sum_j |t_ij|: bfloat16 H and bfloat16 w (expand.hip "H storage": each stored
+# the remainder's tolerance relative to sum_j |t_ij|: bfloat16 H and bfloat16 w (expand_setup.hip "H storage": each stored
 # product moves by <= (1 + 2^-9)^2 - 1 < 2^-8 of its term; the bar leaves a factor 2), float H (float context, real-typed
 # stream: H to float's relative accuracy, fp32 sums of a few hundred terms), fp64
 TOL_REM = {"bf16": 2.0 ** -7, np.float32: 2e-5, np.float64: 1e-11}

@@ -467,9 +467,47 @@ def test_expansion_row_join_equals_sort_join(kernel, shape, sim, dtype, monkeypa
         np.testing.assert_array_equal(out[join][0], out["row"][0], err_msg=join)
 
 
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_expansion_join_fallback_chain(dtype, capfd, monkeypatch):
+    """One setup through the whole chain of join strategies (csrc/expand_setup.hip build_expansion), which is what
+    state shared between them would break: with 8 slots per row (PLSSVM_MI_EXP_RJ_CAP=8) and one pass per row
+    (PLSSVM_MI_EXP_RJ_PMAX=1) on the dense-ish 3000 x 50 @ 40 % set the lower-triangle join gives up, the one-pass join
+    overflows its pass cap, and the sort join builds the rows — the phase lines (PLSSVM_MI_TIMING=1) show that path.
+    Both this setup and one with PLSSVM_MI_EXP_JOIN=sort alone end in the same sort join, so pairs, slots, H storage,
+    layout and the K·p parts are equal, the K·p parts bit for bit."""
+    csr, _ = datagen.sparse_csr(3000, 50, 20, seed=17, dtype=np.float64)
+    x = np.random.default_rng(3).uniform(1, 2, csr[3] - 1).astype(dtype)
+    knobs = ("PLSSVM_MI_EXP_JOIN", "PLSSVM_MI_EXP_RJ", "PLSSVM_MI_EXP_RJ_CAP", "PLSSVM_MI_EXP_RJ_PMAX", "PLSSVM_MI_EXP_LT",
+             "PLSSVM_MI_TIMING")
+
+    def setup(env):
+        for k in knobs:
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        capfd.readouterr()
+        with sparse_svm(csr, "rbf", dtype, algo="expansion") as svm:
+            svm.setup_data_on_device()
+            info = svm.info()
+            assert info["sparse_algo"] == pm._abi.SPARSE_EXPANSION
+            parts = (svm.kp_part(x, "overlap"), svm.kp_part(x, "kernel"))
+        return info, parts, capfd.readouterr().err
+
+    ref, ref_parts, _ = setup({"PLSSVM_MI_EXP_JOIN": "sort"})
+    got, got_parts, err = setup({"PLSSVM_MI_EXP_RJ_CAP": "8", "PLSSVM_MI_EXP_RJ_PMAX": "1", "PLSSVM_MI_TIMING": "1"})
+    assert "expansion: row join (one pass)" in err and "expansion: column join (blocks)" in err, err[-2000:]
+    assert "row join, transpose" not in err, err[-2000:]
+    assert got["exp_lt"] == 0
+    assert ref["pairs"] > 0
+    for key in ("pairs", "pair_slots", "exp_hbytes", "exp_layout"):
+        assert got[key] == ref[key], (key, got[key], ref[key])
+    np.testing.assert_array_equal(got_parts[0], ref_parts[0])
+    np.testing.assert_array_equal(got_parts[1], ref_parts[1])
+
+
 @pytest.mark.parametrize("gamma,want_hbytes", [(None, 2), (0.2, 4)])
 def test_expansion_bf16_remainder_bound(gamma, want_hbytes, monkeypatch):
-    """Remainder storage (expand.hip "H storage"): in a float context H is stored as bfloat16
+    """Remainder storage (expand_setup.hip "H storage"): in a float context H is stored as bfloat16
     when every stored |H_ij| is at most 2^-16 of its pair's kernel value (1 + E(s) for rbf), so rounding H
     (relative error <= 2^-9) moves each pair's term by at most 2^-24 of that kernel value — below the float
     rounding of the kernel value itself. Checked: the default layout is bfloat16 on the BASELINE-like set and
@@ -502,7 +540,7 @@ def test_expansion_bf16_remainder_bound(gamma, want_hbytes, monkeypatch):
                                              ("32768", "2", None), ("auto", "0", (1, 3)), ("auto", "0", (2, 8))])
 @pytest.mark.parametrize("shape", [(140000, 3000, 20), (150000, 200000, 6)])
 def test_expansion_row_flags_equal_row_index(rbb, groups, sim, shape, monkeypatch):
-    """Flagged chunks (expand.hip: no per-chunk row index; bit 14 of a chunk's first bfloat16 H marks a row's
+    """Flagged chunks (expand_setup.hip: no per-chunk row index; bit 14 of a chunk's first bfloat16 H marks a row's
     first chunk of a window, rows without partners in a window get a zero dummy chunk, the kernel numbers rows
     by a ballot of the flags) against the indexed 4-slot chunks: the same stored values in the same order, so
     the K·p and its overlap part are equal bit for bit — across accumulator classes, window groups and
