@@ -411,6 +411,14 @@ PLSSVM_MI_API int plssvm_mi_get_info(const plssvm_mi_ctx *ctx, plssvm_mi_info *i
  * with kp_cache_packed_tiles on the first request after that. An entry point of its own because plssvm_mi_info keeps
  * its size and its last fields (tests/test_predict_multi_abi.py pins them). */
 PLSSVM_MI_API int plssvm_mi_get_kp_cache_narrow_tiles(const plssvm_mi_ctx *ctx, int64_t *narrow_tiles);
+/* The plans of the factored sparse-linear K·p as the setup built them (csrc/spmv.hpp; read-only, nothing selects a
+ * regime): out[0..5] the CSC pass w = X^T p, out[6..11] the CSR pass raw = X w, each {P panels, ldsx (1 = 16-bit
+ * indices into LDS panels, 0 = one panel of 32-bit global indices), W panel width in elements, nblocks workgroups,
+ * nchunks 64-slot chunks, f22 (1 = packed FP22 value stream)}; out[12..15] the row-block CSR pass of the one-GPU CG
+ * with the finalize fused, {P, W, RBK rows per workgroup, nblk workgroups} (nblk = 0: not built, the CG sums the CSR
+ * pass's panel slabs in its finalize). All zeros when the context is not a factored sparse one. An entry point of
+ * its own because plssvm_mi_info keeps its size. */
+PLSSVM_MI_API int plssvm_mi_get_spmv_plan(const plssvm_mi_ctx *ctx, int64_t out[16]);
 
 #ifdef __cplusplus
 }

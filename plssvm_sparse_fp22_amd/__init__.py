@@ -482,6 +482,17 @@ class CSVM:
         self._check(_abi.lib().plssvm_mi_get_predict_stats(self._ctx, out))
         return [int(out[0]), int(out[1])]
 
+    def spmv_plan(self):
+        """The plans of the factored sparse-linear K.p as the setup built them (plssvm_mi_get_spmv_plan): "csc" and
+        "csr", the passes w = X^T p and raw = X w, each {P, ldsx, W, nblocks, nchunks, f22}, and "rb", the row-block
+        CSR pass of the one-GPU CG, {P, W, RBK, nblk}; all zeros when the context is not a factored sparse one."""
+        out = (ctypes.c_int64 * 16)()
+        self._check(_abi.lib().plssvm_mi_get_spmv_plan(self._ctx, out))
+        v = [int(x) for x in out]
+        keys = ("P", "ldsx", "W", "nblocks", "nchunks", "f22")
+        return {"csc": dict(zip(keys, v[0:6])), "csr": dict(zip(keys, v[6:12])),
+                "rb": dict(zip(("P", "W", "RBK", "nblk"), v[12:16]))}
+
     def time_kp_multi(self, nrhs, reps=5):
         a = ctypes.c_double()
         self._check(_abi.lib().plssvm_mi_time_kp_multi(self._ctx, int(nrhs), reps, ctypes.byref(a)))

@@ -34,7 +34,7 @@ EXPORTS = (
     "plssvm_mi_comm_init_host", "plssvm_mi_kp_part", "plssvm_mi_set_progress", "plssvm_mi_comm_abort",
     "plssvm_mi_kp_multi", "plssvm_mi_solve_cg_multi", "plssvm_mi_learn_multi", "plssvm_mi_time_kp_multi",
     "plssvm_mi_predict_multi_dense", "plssvm_mi_predict_multi_csr", "plssvm_mi_get_predict_stats",
-    "plssvm_mi_get_kp_cache_narrow_tiles",
+    "plssvm_mi_get_kp_cache_narrow_tiles", "plssvm_mi_get_spmv_plan",
 )
 # the one entry point a PLSSVM_MI_LIB build may lack (a build from before the narrow record form, loaded for an A/B
 # run): CSVM.info() then reports kp_cache_narrow_tiles = 0, which is what such a build stores
@@ -138,6 +138,7 @@ def _declare(L):
         "plssvm_mi_predict_multi_csr": ([P, P, I64, I64, P, P, P, P, I, I64, I64, P, I64], I),
         "plssvm_mi_get_predict_stats": ([P, PI64], I),
         "plssvm_mi_get_kp_cache_narrow_tiles": ([P, PI64], I),
+        "plssvm_mi_get_spmv_plan": ([P, PI64], I),
     }
     for name, (args, res) in sig.items():
         if name in OPTIONAL_EXPORTS and not hasattr(L, name):

@@ -498,4 +498,26 @@ int plssvm_mi_get_kp_cache_narrow_tiles(const plssvm_mi_ctx *cctx, int64_t *narr
     return ctx->call([&](auto &e) { *narrow_tiles = e.kc.narrow(e); });
 }
 
+int plssvm_mi_get_spmv_plan(const plssvm_mi_ctx *cctx, int64_t out[16]) {
+    if (!cctx || !out) return PLSSVM_MI_ERR_ARG;
+    auto *ctx = const_cast<plssvm_mi_ctx *>(cctx);
+    return ctx->call([&](auto &e) {
+        std::fill(out, out + 16, int64_t(0));
+        if (!e.sparse || !e.factored()) return;
+        int64_t *o = out;
+        for (const auto *pl : { &e.csr.spmv_csc, &e.csr.spmv_csr }) {
+            if (pl->nblocks > 0) {
+                const int64_t v[6] = { pl->P, pl->ldsx ? 1 : 0, pl->W, pl->nblocks, pl->nchunks, pl->val22.get() ? 1 : 0 };
+                std::copy(v, v + 6, o);
+            }
+            o += 6;
+        }
+        const auto &rb = e.csr.rb_csr;
+        if (rb.nblk > 0) {
+            const int64_t v[4] = { rb.P, rb.W, rb.RBK, rb.nblk };
+            std::copy(v, v + 4, o);
+        }
+    });
+}
+
 }  // extern "C"
