@@ -52,6 +52,8 @@ extern "C" {
 #define PLSSVM_MI_KERNEL_LINEAR 0
 #define PLSSVM_MI_KERNEL_POLYNOMIAL 1
 #define PLSSVM_MI_KERNEL_RBF 2
+/* 3 (upstream's sigmoid) is not offered: PLSSVM_MI_ERR_UNSUPPORTED */
+#define PLSSVM_MI_KERNEL_LAPLACIAN 4 /* exp(-gamma * ||x - z||_1); gamma as for rbf, degree and coef0 ignored; dense data only */
 
 /* value formats of sparse feature data (build-defined; the reference has no sparse path) */
 #define PLSSVM_MI_VAL_REAL 0 /* float or double, as the context's real type */
@@ -197,7 +199,11 @@ PLSSVM_MI_API int plssvm_mi_setup_dense(plssvm_mi_ctx *ctx, const void *X, int64
 /* Sparse setup (build-defined format): CSR with int64 rowptr[n+1],
  * int32 col[nnz] ascending per row, values in val_fmt (PLSSVM_MI_VAL_REAL: real[nnz];
  * PLSSVM_MI_VAL_FP22: uint32 packed words, orc/fp22 layout). Semantics == dense setup on the
- * densified matrix (the reference parser densifies, src/plssvm/parameter.cpp:66-87). */
+ * densified matrix (the reference parser densifies, src/plssvm/parameter.cpp:66-87).
+ * A PLSSVM_MI_KERNEL_LAPLACIAN context takes dense data only: plssvm_mi_setup_csr and plssvm_mi_setup_coo return
+ * PLSSVM_MI_ERR_UNSUPPORTED on it (plssvm_mi_last_error says so) and leave the context usable, e.g. for
+ * plssvm_mi_setup_dense. CSR points passed to predict on a dense Laplacian model are densified per chunk as for
+ * the other kernels. */
 PLSSVM_MI_API int plssvm_mi_setup_csr(plssvm_mi_ctx *ctx, const int64_t *rowptr, const int32_t *col, const void *val,
                         int val_fmt, int64_t n, int64_t d);
 
@@ -334,7 +340,8 @@ PLSSVM_MI_API int plssvm_mi_predict_csr(plssvm_mi_ctx *ctx, const void *alpha, d
  * classes, on np, on the point's position in the call, on the chunking of the points, or on the run: row c of OUT is
  * BITWISE what plssvm_mi_predict_dense / _csr return for (alpha_c, bias_c), for any subset or order of the points.
  * Environment, read per call: PLSSVM_MI_PRED_GEMM=1 selects the rocBLAS GEMM + epilogue path for dense poly / rbf
- * (once per class; the A/B baseline), PLSSVM_MI_PRED_CHUNK=<points> overrides the number of points per upload,
+ * (once per class; the A/B baseline; ignored for the Laplacian kernel, which has no GEMM form and always runs the
+ * fused tile kernel), PLSSVM_MI_PRED_CHUNK=<points> overrides the number of points per upload,
  * PLSSVM_MI_PRED_SEQ=1 runs the classes of the linear and sparse paths one after another, each with its own point
  * preparation (the A/B baseline of the shared pass; the same bits). */
 PLSSVM_MI_API int plssvm_mi_predict_multi_dense(plssvm_mi_ctx *ctx, const void *ALPHA, int64_t nclass, int64_t lda,
@@ -352,7 +359,7 @@ PLSSVM_MI_API int plssvm_mi_get_predict_stats(const plssvm_mi_ctx *ctx, int64_t 
 #define PLSSVM_MI_PREDICT_NONE 0      /* no predict call yet */
 #define PLSSVM_MI_PREDICT_LINEAR 1    /* w . z + bias */
 #define PLSSVM_MI_PREDICT_GEMM 2      /* dense poly / rbf: rocBLAS G = X Z^T + epilogue (PLSSVM_MI_PRED_GEMM) */
-#define PLSSVM_MI_PREDICT_TILES 3     /* dense poly / rbf: the fused MFMA tile kernel */
+#define PLSSVM_MI_PREDICT_TILES 3     /* dense poly / rbf: the fused MFMA tile kernel; dense laplacian: its VALU twin */
 #define PLSSVM_MI_PREDICT_EXPANSION 4 /* sparse poly / rbf: the kernel expansion */
 #define PLSSVM_MI_PREDICT_BRUTE 5     /* sparse poly / rbf: every support vector entry per 64 points */
 /* support-vector tiles (of tile_rows rows) per workgroup segment of the fused predict kernel */

@@ -194,6 +194,9 @@ class CSVM:
                 raise ValueError("Data set is empty!")
             if params.data.shape[1] == 0:
                 raise ValueError("No features provided for the data points!")
+        if KERNELS[params.kernel] == KERNELS["laplacian"] and params.data is None:
+            raise ValueError("The Laplacian kernel takes dense data: parse the file with sparse=False (there is no sparse "
+                             "L1-distance K.p)")
         self.params = params
         self.dtype = params.real_type
         self.num_data_points = params.num_data_points

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("PLSSVM_MI_LIB") or os.path.join(_HERE, "libplssvm_mi3
 OK = 0
 ERR = {-1: "ERR_ARG", -2: "ERR_HIP", -3: "ERR_RCCL", -4: "ERR_OOM", -5: "ERR_UNSUPPORTED", -6: "ERR_STATE",
        -7: "ERR_NODEV"}
-KERNELS = {"linear": 0, "polynomial": 1, "poly": 1, "rbf": 2}
+KERNELS = {"linear": 0, "polynomial": 1, "poly": 1, "rbf": 2, "laplacian": 4}  # 3 (upstream's sigmoid) is not offered
 VAL_REAL, VAL_FP22 = 0, 1
 KP_AUTO, KP_PAIRWISE, KP_FACTORED = 0, 1, 2
 OPT_KP_MODE = 1

@@ -47,6 +47,7 @@ struct plssvm_mi_ctx {
 
 namespace {
 thread_local std::string g_create_error;
+static_assert(plssvm_mi::KF_LAPLACIAN == PLSSVM_MI_KERNEL_LAPLACIAN, "the kernels' id and the header's");
 }
 
 extern "C" {
@@ -62,7 +63,7 @@ int plssvm_mi_create(int real_bytes, int kernel, int degree, double gamma, doubl
     if (out == nullptr) return PLSSVM_MI_ERR_ARG;
     *out = nullptr;
     if (real_bytes != 4 && real_bytes != 8) return PLSSVM_MI_ERR_ARG;
-    if (kernel < 0 || kernel > 2) return PLSSVM_MI_ERR_UNSUPPORTED;  // unsupported_kernel_type_exception
+    if (kernel < 0 || (kernel > 2 && kernel != PLSSVM_MI_KERNEL_LAPLACIAN)) return PLSSVM_MI_ERR_UNSUPPORTED;  // unsupported_kernel_type_exception
     if (kernel == 1 && degree < 0) return PLSSVM_MI_ERR_ARG;
     if (!(cost > 0)) return PLSSVM_MI_ERR_ARG;
     const int ndev = plssvm_mi_device_count();
@@ -191,7 +192,10 @@ int plssvm_mi_setup_dense(plssvm_mi_ctx *ctx, const void *X, int64_t n, int64_t 
 int plssvm_mi_setup_csr(plssvm_mi_ctx *ctx, const int64_t *rowptr, const int32_t *col, const void *val, int val_fmt,
                         int64_t n, int64_t d) {
     if (!ctx) return PLSSVM_MI_ERR_ARG;
-    return ctx->call([&](auto &e) { e.setup_csr(rowptr, col, val, val_fmt, n, d); });
+    return ctx->call([&](auto &e) {
+        e.need_dense_kernel_data();
+        e.setup_csr(rowptr, col, val, val_fmt, n, d);
+    });
 }
 
 int plssvm_mi_setup_coo(plssvm_mi_ctx *ctx, const int64_t *row, const int32_t *col, const void *val, int val_fmt,
@@ -200,6 +204,7 @@ int plssvm_mi_setup_coo(plssvm_mi_ctx *ctx, const int64_t *row, const int32_t *c
     return ctx->call([&](auto &e) {
         using T = std::remove_reference_t<decltype(e.gamma)>;
         using plssvm_mi::mi_error;
+        e.need_dense_kernel_data();
         if (n < 1 || d < 1) throw mi_error(PLSSVM_MI_ERR_ARG, "Data set is empty!");
         if (nnz < 0 || (nnz > 0 && (!row || !col || !val))) throw mi_error(PLSSVM_MI_ERR_ARG, "COO arrays missing");
         if (val_fmt != PLSSVM_MI_VAL_REAL && val_fmt != PLSSVM_MI_VAL_FP22) throw mi_error(PLSSVM_MI_ERR_ARG, "unknown value format");

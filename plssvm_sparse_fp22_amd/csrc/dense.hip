@@ -86,6 +86,9 @@ __global__ __launch_bounds__(256) void q_dense_kernel(kfun<T> kf, const T *__res
             v = fma(diff, diff, v);
         }
         q[i] = exp(-kf.gamma * v);
+    } else if (kf.kernel == KF_LAPLACIAN) {
+        for (int64_t k = 0; k < d; ++k) v += __builtin_elementwise_abs(XT[k * n_pad + i] - xlast[k]);
+        q[i] = exp(-kf.gamma * v);
     } else {
         for (int64_t k = 0; k < d; ++k) v = fma(XT[k * n_pad + i], xlast[k], v);
         if (kf.kernel == 0) {

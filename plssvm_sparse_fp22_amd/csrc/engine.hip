@@ -28,6 +28,10 @@ T host_kernel(int kernel, int degree, T gamma, T coef0, const T *a, const T *b, 
         }
         return std::exp(-gamma * v);
     }
+    if (kernel == KF_LAPLACIAN) {
+        for (int64_t k = 0; k < d; ++k) v += std::fabs(a[k] - b[k]);
+        return std::exp(-gamma * v);
+    }
     for (int64_t k = 0; k < d; ++k) v = std::fma(a[k], b[k], v);
     if (kernel == 0) return v;
     return std::pow(std::fma(gamma, v, coef0), (T) degree);
@@ -80,6 +84,12 @@ void partition_superblocks(int64_t nb, int rank, int world, int64_t &s0, int64_t
     s1 = rank == world - 1 ? s_total : split(rank + 1);
     if (s1 < s0) s1 = s0;
     tiles_local = cum[s1] - cum[s0];
+}
+
+template <typename T>
+void engine<T>::need_dense_kernel_data() const {
+    if (kernel == KF_LAPLACIAN)
+        throw mi_error(-5, "The Laplacian kernel takes dense data: use plssvm_mi_setup_dense (no sparse L1-distance K.p)");
 }
 
 template <typename T>

@@ -223,6 +223,7 @@ struct engine : engine_base {
     T cost_inv() const { return T(1) / cost; }
     bool factored() const;
     void need_data() const;
+    void need_dense_kernel_data() const;  // the sparse setups' first check: throws on a kernel that takes dense data only
     void need_q() const;
 
     void comm_init(int rank_, int world_, const void *uid);

@@ -8,9 +8,12 @@
 namespace plssvm_mi {
 
 // kernel parameters of the LS-SVM kernel function (include/plssvm/kernel_types.hpp:63-85)
+// exp(-gamma ||x - z||_1): not a function of x . z, so the dense tile kernels accumulate L1 distances on the VALU
+// instead of a Gram block on MFMA (kp_tiles.hip, predict_tiles.hip). Dense data only; PLSSVM_MI_KERNEL_LAPLACIAN
+constexpr int KF_LAPLACIAN = 4;
 template <typename T>
 struct kfun {
-    int kernel;  // 0 linear, 1 polynomial, 2 rbf
+    int kernel;  // 0 linear, 1 polynomial, 2 rbf, KF_LAPLACIAN
     int degree;
     T gamma;
     T coef0;
@@ -31,9 +34,11 @@ struct cg_scalars {
 // tile edge of the implicit Q~ tiles (rows and columns); n_pad is a multiple of this.
 constexpr int KP_TILE = 128;
 // K-chunk depth of the pairwise tile kernel: 8 (fp64) / 16 (fp32) keeps LDS at <= 49 KB for 3
-// workgroups per CU
+// workgroups per CU. The Laplacian instances (VALU K loop, 2 fp64 workgroups per CU: 70 KB each) take 16 in both types:
+// their next chunk's DMA is issued behind the chunk's last LDS reads and its latency shows at the chunk barrier, so a
+// deeper chunk halves how often
 template <typename T, int KERNEL>
-constexpr int kp_bk() { return sizeof(T) == 8 ? 8 : 16; }
+constexpr int kp_bk() { return (sizeof(T) == 8 && KERNEL != KF_LAPLACIAN) ? 8 : 16; }
 // feature padding of the device layout: a multiple of every chunk depth
 template <typename T>
 constexpr int kp_dpad() { return 16; }

@@ -17,6 +17,7 @@ __device__ __forceinline__ T kernel_apply(int kernel, int degree, T gamma, T coe
         for (int e = 0; e < degree; ++e) r *= base;
         return r;
     }
+    if (kernel == KF_LAPLACIAN) return exp(-gamma * g);  // g = the accumulated L1 distance: no norms, nothing to clamp
     T dist = ni + nj - T(2) * g;
     dist = dist > T(0) ? dist : T(0);
     return exp(-gamma * dist);
@@ -113,6 +114,61 @@ __device__ __forceinline__ double exp_scaled_f64(double y, const double *tab) {
     const int j = (int) jn;  // saturates for huge |y|: the ldexp below then returns 0
     return ldexp(tab[j & (EXP_TAB - 1)] * pr, j >> 8);
 }
+
+// The Laplacian tile kernels' K step. Feature k of the staged chunk (A, B: the [BK][128] row and column panels in LDS)
+// updates all 64 pairs of the lane, acc[mt][nt][r] += |A[k][row] - B[k][col]|, with the MFMA accumulator ownership
+// (row = wr * 64 + mt * 16 + M::row(lane, r), col = wc * 64 + nt * 16 + (lane & 15)), so everything downstream of "a
+// lane holds 64 kernel values in (mt, r, nt) order" applies unchanged. Per feature: 16 row values (the 16 lanes of a
+// group read the same addresses: broadcast, no bank conflicts; fp32: four 16-byte reads) and 4 column values (stride
+// 16) against 128 VALU operations (subtract, add |.|): VALU-issue-bound. The features go in ascending k: every pair's
+// sum is a sequential chain in feature order. L1_CHUNK is the chunk loop both tile kernels share: feature k + 1's
+// operands are read while feature k is accumulated (two register sets, two features per turn). The loop stays rolled:
+// unrolled over the chunk, the compiler rotates it into "all of the chunk's LDS reads, then all of its arithmetic"
+// (320 live operands, 500 spilled registers; a scheduling barrier per feature does not stop that, it happens before
+// instruction scheduling). NEXT_CHUNK runs behind the chunk's last LDS reads, under the last feature's arithmetic.
+template <typename T>
+__device__ __forceinline__ void l1_load(const T *A, const T *B, int k, int wr, int wc, int lane, T (&a)[4][4], T (&b)[4]) {
+    using M = mfma16<T>;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) a[mt][r] = A[k * KP_TILE + wr * 64 + mt * 16 + M::row(lane, r)];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) b[nt] = B[k * KP_TILE + wc * 64 + nt * 16 + (lane & 15)];
+}
+// acc += |a - b|. fp32: the add is written out with its |.| source modifier: left to itself -O3 packs neighbouring pairs
+// into v_pk_add_f32, which has no |.| and so needs a v_and_b32 per value first (2.4 VALU operations per pair, not 2)
+__device__ __forceinline__ float l1_acc(float acc, float a, float b) {
+    const float d = a - b;
+    asm("v_add_f32_e64 %0, %0, |%1|" : "+v"(acc) : "v"(d));
+    return acc;
+}
+__device__ __forceinline__ double l1_acc(double acc, double a, double b) { return acc + __builtin_elementwise_abs(a - b); }
+template <typename T, typename ACC>
+__device__ __forceinline__ void l1_update(ACC (&acc)[4][4], const T (&a)[4][4], const T (&b)[4]) {
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[mt][nt][r] = l1_acc(acc[mt][nt][r], a[mt][r], b[nt]);
+}
+#define L1_CHUNK(T, BK, A, B, wr, wc, lane, acc, NEXT_CHUNK)                           \
+    {                                                                                  \
+        static_assert(BK % 2 == 0, "two features per turn");                           \
+        T l1a0[4][4], l1b0[4], l1a1[4][4], l1b1[4];                                    \
+        l1_load<T>(A, B, 0, wr, wc, lane, l1a0, l1b0);                                 \
+        _Pragma("unroll 1") for (int k = 0; k < BK; k += 2) {                          \
+            l1_load<T>(A, B, k + 1, wr, wc, lane, l1a1, l1b1);                         \
+            l1_update<T>(acc, l1a0, l1b0);                                             \
+            /* the last turn reads feature BK - 1 again: one spare set of reads per chunk, no branch around them */ \
+            l1_load<T>(A, B, k + 2 < BK ? k + 2 : BK - 1, wr, wc, lane, l1a0, l1b0);   \
+            if (k + 2 >= BK) {                                                         \
+                NEXT_CHUNK;                                                            \
+            }                                                                          \
+            l1_update<T>(acc, l1a1, l1b1);                                             \
+        }                                                                              \
+    }
 
 // 16 B per lane global -> LDS through a buffer descriptor on a wave-uniform base: the per-lane part is
 // voff, a wave-uniform offset goes in soff (SGPR), so no VALU address math is needed per load

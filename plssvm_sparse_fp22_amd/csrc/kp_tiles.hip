@@ -30,8 +30,11 @@ namespace {
 // occupancy: 3 workgroups per CU (<= 49 KB LDS, <= 168 VGPRs) hide the chunk barriers / DMA waits
 // best; the fp64 RBF variant spills a few epilogue values at that budget (outside the K loop), and
 // still runs as fast as with 2 workgroups and 16-deep chunks
+// The fp64 Laplacian instances run 2 per CU: the VALU K loop keeps the 128 accumulator registers plus one feature's 16
+// row and 4 column values (40 registers) and the next feature's reads in flight, which does not fit 168 VGPRs; the loop
+// is VALU-issue-bound, so two waves per SIMD are enough to cover the LDS reads and the chunk barrier. fp32 fits 3.
 template <typename T, int KERNEL>
-constexpr int kp_waves_per_eu() { return 3; }
+constexpr int kp_waves_per_eu() { return (KERNEL == KF_LAPLACIAN && sizeof(T) == 8) ? 2 : 3; }
 
 // fp64 RBF: chunk kc+1's DMA is issued after chunk kc's LDS reads; every other instance: right after the barrier.
 // Same box, round 6 (profiles/r06_kp_dma_order_ab.json): config 2 (fp64 RBF) 39.51 / 39.58 ms against 39.62 / 39.67 ms
@@ -42,6 +45,7 @@ constexpr int kp_waves_per_eu() { return 3; }
 #endif
 template <typename T, int KERNEL>
 constexpr bool kp_dma_after_reads() {
+    if (KERNEL == KF_LAPLACIAN) return true;  // behind the chunk's last LDS reads (its K loop reads feature by feature)
     return KP_DMA_AFTER_READS == 2 ? (sizeof(T) == 8 && KERNEL == 2) : KP_DMA_AFTER_READS == 1;
 }
 
@@ -467,26 +471,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_wav
             if (!kp_dma_after_reads<T, KERNEL>() && kc + 1 < nk) issue(kc + 1, (int) ((kc + 1) & 1));
             const T *A = smem + OFF_PAN + (2 * (kc & 1)) * PANEL;
             const T *B = A + PANEL;
-            // fp64 RBF: the whole chunk's operands come out of LDS before chunk kc+1's DMA is issued — the compiler cannot
-            // tell the DMA's LDS target from the buffer being read, so an LDS read issued after the DMA waits for it
-            // (vmcnt(0)) and the prefetch sits on each wave's critical path instead of under its MFMAs (the other instances
-            // measured faster with the DMA first, see kp_dma_after_reads)
-            T a[BK / 4][4], b[BK / 4][4];
+            if constexpr (KERNEL == KF_LAPLACIAN) {
+                // no MFMA form: L1_CHUNK (kp_device.hpp), feature by feature in ascending k. Chunk kc+1's DMA goes
+                // out behind the chunk's last LDS reads, under the last feature's 128 VALU operations (an LDS read issued
+                // after the DMA would wait for it, see below)
+                L1_CHUNK(T, BK, A, B, wr, wc, lane, acc, if (kc + 1 < nk) issue(kc + 1, (int) ((kc + 1) & 1)));
+            } else {
+                // fp64 RBF: the whole chunk's operands come out of LDS before chunk kc+1's DMA is issued — the compiler cannot
+                // tell the DMA's LDS target from the buffer being read, so an LDS read issued after the DMA waits for it
+                // (vmcnt(0)) and the prefetch sits on each wave's critical path instead of under its MFMAs (the other instances
+                // measured faster with the DMA first, see kp_dma_after_reads)
+                T a[BK / 4][4], b[BK / 4][4];
 #pragma unroll
-            for (int ks = 0; ks < BK / 4; ++ks) {
-                const int kr = ks * 4 + (lane >> 4);
+                for (int ks = 0; ks < BK / 4; ++ks) {
+                    const int kr = ks * 4 + (lane >> 4);
 #pragma unroll
-                for (int mt = 0; mt < 4; ++mt) a[ks][mt] = A[kr * KP_TILE + wr * 64 + mt * 16 + (lane & 15)];
+                    for (int mt = 0; mt < 4; ++mt) a[ks][mt] = A[kr * KP_TILE + wr * 64 + mt * 16 + (lane & 15)];
 #pragma unroll
-                for (int nt = 0; nt < 4; ++nt) b[ks][nt] = B[kr * KP_TILE + wc * 64 + nt * 16 + (lane & 15)];
+                    for (int nt = 0; nt < 4; ++nt) b[ks][nt] = B[kr * KP_TILE + wc * 64 + nt * 16 + (lane & 15)];
+                }
+                if (kp_dma_after_reads<T, KERNEL>() && kc + 1 < nk) issue(kc + 1, (int) ((kc + 1) & 1));
+#pragma unroll
+                for (int ks = 0; ks < BK / 4; ++ks)
+#pragma unroll
+                    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                        for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = M::op(a[ks][mt], b[ks][nt], acc[mt][nt]);
             }
-            if (kp_dma_after_reads<T, KERNEL>() && kc + 1 < nk) issue(kc + 1, (int) ((kc + 1) & 1));
-#pragma unroll
-            for (int ks = 0; ks < BK / 4; ++ks)
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = M::op(a[ks][mt], b[ks][nt], acc[mt][nt]);
         }
     }
 
@@ -793,7 +804,9 @@ void launch_kp_mode(const kp_geom<T> &g, const T *p, T *partial, int64_t base, i
         switch (g.kf.kernel) {
             case 0: KP_LAUNCH(0); break;
             case 1: KP_LAUNCH(1); break;
-            default: KP_LAUNCH(2); break;
+            case 2: KP_LAUNCH(2); break;
+            case KF_LAPLACIAN: KP_LAUNCH(KF_LAPLACIAN); break;
+            default: throw mi_error(-5, "unknown kernel function for the pairwise tile kernel");
         }
     }
 #undef KP_LAUNCH
@@ -849,7 +862,9 @@ void launch_kp_tiles_multi(const kp_geom<T> &g, const T *p, int64_t pstride, T *
         switch (g.kf.kernel) {
             case 0: KP_LAUNCH(0, KP_COMPUTE, cached, g.wgs - cached); break;
             case 1: KP_LAUNCH(1, KP_COMPUTE, cached, g.wgs - cached); break;
-            default: KP_LAUNCH(2, KP_COMPUTE, cached, g.wgs - cached); break;
+            case 2: KP_LAUNCH(2, KP_COMPUTE, cached, g.wgs - cached); break;
+            case KF_LAPLACIAN: KP_LAUNCH(KF_LAPLACIAN, KP_COMPUTE, cached, g.wgs - cached); break;
+            default: throw mi_error(-5, "unknown kernel function for the batched pairwise tile kernel");
         }
         MI_LAUNCH_CHECK();
     }

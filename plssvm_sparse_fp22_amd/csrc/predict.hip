@@ -597,7 +597,8 @@ void engine<T>::predict_multi(const T *alpha_host, int64_t nclass, int64_t lda, 
     const char *ge = std::getenv("PLSSVM_MI_PRED_GEMM");
     const bool gemm = ge != nullptr && std::strcmp(ge, "0") != 0;
     predict_uploads = 0;
-    if (!sparse && kernel != 0 && !gemm) {
+    // (the Laplacian kernel has no Gram block for rocBLAS to form: always the tile kernel, PLSSVM_MI_PRED_GEMM ignored)
+    if (!sparse && kernel != 0 && (!gemm || kernel == KF_LAPLACIAN)) {
         predict_tiles(alpha_host, nclass, lda, bias, Z, zrowptr, zcol, zval, zfmt, np, out, ldo);
         return;
     }

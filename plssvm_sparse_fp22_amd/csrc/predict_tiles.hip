@@ -23,6 +23,11 @@
 // Padding: padded support-vector rows have zero XT columns, zero norms and zero alpha; their kernel value is finite
 // (poly: coef0^degree, RBF: exp(-gamma |z|^2) <= 1), so its product with alpha = 0 is exactly 0. Padded points are
 // computed and never stored.
+//
+// The Laplacian kernel exp(-gamma ||x - z||_1) has no Gram form: its instance keeps the work units, the DMA, the
+// accumulator ownership, the class turns and the sums, and replaces the MFMA K loop by L1 accumulation on the VALU
+// (L1_CHUNK, kp_device.hpp). Its padding: zero features add |0 - 0|, a padded support-vector row gives
+// exp(-gamma ||z||_1) in (0, 1] times alpha = 0.
 #include "kernels.hpp"
 #include "kp_device.hpp"
 
@@ -36,15 +41,18 @@ namespace {
 #define PRED_TILE_WAVES 3
 #endif
 constexpr int PRED_WAVES = PRED_TILE_WAVES;
+// the fp64 Laplacian instance: 2 per CU, as its kp_tile_kernel twin (kp_waves_per_eu: the VALU K loop's registers)
+template <typename T, int KERNEL>
+constexpr int pred_waves() { return (KERNEL == KF_LAPLACIAN && sizeof(T) == 8) ? 2 : PRED_WAVES; }
 // tiles of a super-block edge: 8 point tiles x 8 segments share their panels in one XCD's L2
 constexpr int PRED_SUPER = 8;
 
 template <typename T, int KERNEL>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PRED_WAVES, PRED_WAVES))) void predict_tile_kernel(
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(pred_waves<T, KERNEL>(), pred_waves<T, KERNEL>()))) void predict_tile_kernel(
     kfun<T> kf, const T *__restrict__ XT, const T *__restrict__ norms, int64_t n_pad, int64_t nb,
     const T *__restrict__ ZT, const T *__restrict__ znorms, int64_t np_pad, int64_t npt, int64_t nseg, int64_t d_pad,
     const T *__restrict__ A, int ncls, T *__restrict__ part) {
-    static_assert(KERNEL == 1 || KERNEL == 2, "linear predicts through w . z");
+    static_assert(KERNEL == 1 || KERNEL == 2 || KERNEL == KF_LAPLACIAN, "linear predicts through w . z");
     using M = mfma16<T>;
     using acc_t = typename M::acc_t;
     constexpr int BK = kp_bk<T, KERNEL>();
@@ -61,6 +69,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PRED_WAVES,
     __shared__ __attribute__((aligned(16))) T smem[SMEM];
     __shared__ T run[KP_MULTI_W * KP_TILE];  // running sums [class][point] of the segment
     constexpr bool FAST_EXP = (KERNEL == 2) && sizeof(T) == 8;
+    constexpr bool DMA_LATE = FAST_EXP || KERNEL == KF_LAPLACIAN;  // the next chunk's DMA after this chunk's LDS reads
     __shared__ double exp_tab[FAST_EXP ? EXP_TAB : 1];
 
     // workgroup -> (point tile P, segment S): bands of PRED_SUPER point tiles, inside a band super-blocks of
@@ -145,27 +154,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PRED_WAVES,
         for (int64_t kc = 0; kc < nk; ++kc) {
             if (kc > 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();  // chunk kc visible to all waves; every wave is done reading chunk kc-1
-            if (!FAST_EXP && kc + 1 < nk) issue(kc + 1, (int) ((kc + 1) & 1));
+            if (!DMA_LATE && kc + 1 < nk) issue(kc + 1, (int) ((kc + 1) & 1));
             const T *Ap = smem + OFF_PAN + (2 * (kc & 1)) * PANEL;
             const T *Bp = Ap + PANEL;
-            T a[BK / 4][4], b[BK / 4][4];
+            if constexpr (KERNEL == KF_LAPLACIAN) {
+                // kp_tile_kernel's Laplacian K loop: L1 distances on the VALU, feature by feature (L1_CHUNK, kp_device.hpp;
+                // rows = points, columns = support vectors), the next chunk's DMA behind the chunk's last LDS reads
+                L1_CHUNK(T, BK, Ap, Bp, wr, wc, lane, acc, if (kc + 1 < nk) issue(kc + 1, (int) ((kc + 1) & 1)));
+            } else {
+                T a[BK / 4][4], b[BK / 4][4];
 #pragma unroll
-            for (int ks = 0; ks < BK / 4; ++ks) {
-                const int kr = ks * 4 + (lane >> 4);
+                for (int ks = 0; ks < BK / 4; ++ks) {
+                    const int kr = ks * 4 + (lane >> 4);
 #pragma unroll
-                for (int mt = 0; mt < 4; ++mt) a[ks][mt] = Ap[kr * KP_TILE + wr * 64 + mt * 16 + (lane & 15)];
+                    for (int mt = 0; mt < 4; ++mt) a[ks][mt] = Ap[kr * KP_TILE + wr * 64 + mt * 16 + (lane & 15)];
 #pragma unroll
-                for (int nt = 0; nt < 4; ++nt) b[ks][nt] = Bp[kr * KP_TILE + wc * 64 + nt * 16 + (lane & 15)];
+                    for (int nt = 0; nt < 4; ++nt) b[ks][nt] = Bp[kr * KP_TILE + wc * 64 + nt * 16 + (lane & 15)];
+                }
+                // fp64 RBF: the next chunk's DMA after this chunk's LDS reads, every other MFMA instance right after the
+                // barrier (kp_tile_kernel's measured order, kp_dma_after_reads)
+                if (DMA_LATE && kc + 1 < nk) issue(kc + 1, (int) ((kc + 1) & 1));
+#pragma unroll
+                for (int ks = 0; ks < BK / 4; ++ks)
+#pragma unroll
+                    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                        for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = M::op(a[ks][mt], b[ks][nt], acc[mt][nt]);
             }
-            // fp64 RBF: the next chunk's DMA after this chunk's LDS reads, every other instance right after the
-            // barrier (kp_tile_kernel's measured order, kp_dma_after_reads)
-            if (FAST_EXP && kc + 1 < nk) issue(kc + 1, (int) ((kc + 1) & 1));
-#pragma unroll
-            for (int ks = 0; ks < BK / 4; ++ks)
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = M::op(a[ks][mt], b[ks][nt], acc[mt][nt]);
         }
 
         int te = tid;
@@ -234,7 +249,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PRED_WAVES,
 
 // out[c][p] = ((sum over the segments, in order, of part[c][s][p]) + alpha_c[m] k(x_m, z_p)) + bias_c; one thread per
 // point, x_m . z_p a sequential fma chain in feature order. ab = [alpha_c[m] for every class | bias_c for every class]
-template <typename T>
+// L1 (the Laplacian kernel): the last support vector's term needs ||x_m - z_p||_1 instead of x_m . z_p and norms
+template <typename T, bool L1>
 __global__ __launch_bounds__(256) void predict_finish_kernel(kfun<T> kf, const T *__restrict__ part, int64_t nseg,
                                                              const T *__restrict__ ZT, const T *__restrict__ znorms,
                                                              int64_t np_pad, int64_t d, const T *__restrict__ xlast,
@@ -242,9 +258,15 @@ __global__ __launch_bounds__(256) void predict_finish_kernel(kfun<T> kf, const T
                                                              int64_t np, T *__restrict__ out) {
     const int64_t p = (int64_t) blockIdx.x * 256 + threadIdx.x;
     if (p >= np) return;
-    T dl = 0;
-    for (int64_t k = 0; k < d; ++k) dl = fma(xlast[k], ZT[k * np_pad + p], dl);
-    const T kl = kernel_apply<T>(kf.kernel, kf.degree, kf.gamma, kf.coef0, dl, nlast, kf.kernel == 2 ? znorms[p] : T(0));
+    T dl = 0, kl;
+    if constexpr (L1) {
+        for (int64_t k = 0; k < d; ++k) dl += __builtin_elementwise_abs(ZT[k * np_pad + p] - xlast[k]);
+        kl = kernel_apply<T>(KF_LAPLACIAN, kf.degree, kf.gamma, kf.coef0, dl, T(0), T(0));
+    } else {
+        __builtin_assume(kf.kernel != KF_LAPLACIAN);  // kernel_apply's Laplacian case is the L1 instance's alone
+        for (int64_t k = 0; k < d; ++k) dl = fma(xlast[k], ZT[k * np_pad + p], dl);
+        kl = kernel_apply<T>(kf.kernel, kf.degree, kf.gamma, kf.coef0, dl, nlast, kf.kernel == 2 ? znorms[p] : T(0));
+    }
     for (int c = 0; c < ncls; ++c) {
         T s = 0;
         for (int64_t g = 0; g < nseg; ++g) s += part[((int64_t) c * nseg + g) * np_pad + p];
@@ -260,7 +282,8 @@ void launch_predict_tiles(kfun<T> kf, const T *XT, const T *norms, int64_t n_pad
                           hipStream_t s) {
     if (nb <= 0 || npoints <= 0) return;
     if (ncls < 1 || ncls > KP_MULTI_W) throw mi_error(-1, "bad class count for the predict tile kernel");
-    if (kf.kernel != 1 && kf.kernel != 2) throw mi_error(-1, "the predict tile kernel serves the polynomial and rbf kernels");
+    if (kf.kernel != 1 && kf.kernel != 2 && kf.kernel != KF_LAPLACIAN)
+        throw mi_error(-1, "the predict tile kernel serves the polynomial, rbf and Laplacian kernels");
     if (n_pad % KP_TILE != 0 || np_pad % KP_TILE != 0 || d_pad % kp_dpad<T>() != 0 || nb * KP_TILE > n_pad ||
         npoints > np_pad)
         throw mi_error(-1, "bad padding for the predict tile kernel");
@@ -273,9 +296,12 @@ void launch_predict_tiles(kfun<T> kf, const T *XT, const T *norms, int64_t n_pad
     if (kf.kernel == 1)
         hipLaunchKernelGGL((predict_tile_kernel<T, 1>), grid, block, 0, s, kf, XT, norms, n_pad, nb, ZT, znorms, np_pad, npt,
                            nseg, d_pad, A, ncls, part);
-    else
+    else if (kf.kernel == 2)
         hipLaunchKernelGGL((predict_tile_kernel<T, 2>), grid, block, 0, s, kf, XT, norms, n_pad, nb, ZT, znorms, np_pad, npt,
                            nseg, d_pad, A, ncls, part);
+    else
+        hipLaunchKernelGGL((predict_tile_kernel<T, KF_LAPLACIAN>), grid, block, 0, s, kf, XT, norms, n_pad, nb, ZT, znorms,
+                           np_pad, npt, nseg, d_pad, A, ncls, part);
     MI_LAUNCH_CHECK();
 }
 
@@ -284,8 +310,12 @@ void launch_predict_finish(kfun<T> kf, const T *part, int64_t nseg, const T *ZT,
                            int64_t d, const T *xlast, T nlast, const T *ab, int ncls, int nclass, int64_t np, T *out,
                            hipStream_t s) {
     if (np <= 0 || ncls <= 0) return;
-    hipLaunchKernelGGL(predict_finish_kernel<T>, dim3((unsigned) ceil_div(np, 256)), dim3(256), 0, s, kf, part, nseg, ZT,
-                       znorms, np_pad, d, xlast, nlast, ab, ncls, nclass, np, out);
+    if (kf.kernel == KF_LAPLACIAN)
+        hipLaunchKernelGGL((predict_finish_kernel<T, true>), dim3((unsigned) ceil_div(np, 256)), dim3(256), 0, s, kf, part, nseg,
+                           ZT, znorms, np_pad, d, xlast, nlast, ab, ncls, nclass, np, out);
+    else
+        hipLaunchKernelGGL((predict_finish_kernel<T, false>), dim3((unsigned) ceil_div(np, 256)), dim3(256), 0, s, kf, part, nseg,
+                           ZT, znorms, np_pad, d, xlast, nlast, ab, ncls, nclass, np, out);
     MI_LAUNCH_CHECK();
 }
 

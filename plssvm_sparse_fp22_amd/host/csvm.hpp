@@ -309,7 +309,7 @@ class csvm : public csvm_interface<T> {
         out += "\n";
         if (p.kernel == kernel_type::polynomial) {
             out += "degree " + std::to_string(p.degree) + "\ngamma " + shortest(p.gamma) + "\ncoef0 " + shortest(p.coef0) + "\n";
-        } else if (p.kernel == kernel_type::rbf) {
+        } else if (p.kernel == kernel_type::rbf || p.kernel == kernel_type::laplacian) {
             out += "gamma " + shortest(p.gamma) + "\n";
         }
         out += "nr_class 2\ntotal_sv " + std::to_string(npos + nneg) + "\nrho " + shortest(-bias_) +

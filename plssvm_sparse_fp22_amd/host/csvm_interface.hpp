@@ -110,6 +110,10 @@ class csvm_interface {
     // kernel_function<k> (include/plssvm/kernel_types.hpp:63-85): sequential fma chains
     [[nodiscard]] real_type kernel_function(const std::vector<real_type> &xi, const std::vector<real_type> &xj) const {
         T v = 0;
+        if (kernel_ == kernel_type::laplacian) {
+            for (std::size_t k = 0; k < xi.size(); ++k) v += std::fabs(xi[k] - xj[k]);
+            return std::exp(-gamma_ * v);
+        }
         if (kernel_ == kernel_type::rbf) {
             for (std::size_t k = 0; k < xi.size(); ++k) {
                 const T diff = xi[k] - xj[k];

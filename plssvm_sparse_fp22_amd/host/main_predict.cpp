@@ -57,6 +57,10 @@ int predict(const cli &c) {
     test.parse_test_file(c.pos[0], sparse, 0, true);
     model.parse_model_file(c.pos[1], sparse, test.num_features);
     if (test.num_features < model.num_features) test.parse_test_file(c.pos[0], sparse, model.num_features, true);
+    if (model.kernel == kernel_type::laplacian && sparse) {
+        std::fprintf(stderr, "The model's laplacian kernel takes dense input: it cannot be combined with --sparse!\n");
+        return EXIT_FAILURE;
+    }
     const bool multi = model.nr_class >= 3;
     if (print_info) {
         std::printf("\ntask: prediction\nkernel type: %s -> ", kernel_name(model.kernel));
@@ -66,6 +70,7 @@ int predict(const cli &c) {
                 std::printf("(gamma*u'*v + coef0)^degree\ngamma: %s\ncoef0: %s\ndegree: %d\n",
                             csvm<T>::shortest(model.gamma).c_str(), csvm<T>::shortest(model.coef0).c_str(), model.degree);
                 break;
+            case kernel_type::laplacian: std::printf("exp(-gamma*|u-v|_1)\ngamma: %s\n", csvm<T>::shortest(model.gamma).c_str()); break;
             default: std::printf("exp(-gamma*|u-v|^2)\ngamma: %s\n", csvm<T>::shortest(model.gamma).c_str()); break;
         }
         std::string rho = csvm<T>::shortest(model.rho);

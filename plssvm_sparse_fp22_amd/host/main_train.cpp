@@ -28,7 +28,8 @@ const char *kHelp =
     "  -t, --kernel_type arg      set type of kernel function.\n"
     "                                  0 -- linear: u'*v\n"
     "                                  1 -- polynomial: (gamma*u'*v + coef0)^degree\n"
-    "                                  2 -- radial basis function: exp(-gamma*|u-v|^2) (default: 0)\n"
+    "                                  2 -- radial basis function: exp(-gamma*|u-v|^2)\n"
+    "                                  4 -- laplacian: exp(-gamma*|u-v|_1), dense input only (default: 0)\n"
     "  -d, --degree arg           set degree in kernel function (default: 3)\n"
     "  -g, --gamma arg            set gamma in kernel function (default: 1 / num_features)\n"
     "  -r, --coef0 arg            set coef0 in kernel function (default: 0)\n"
@@ -77,6 +78,10 @@ int train(const cli &c) {
     }
     params.input_filename = c.pos[0];
     if (c.pos.size() > 1) params.model_filename = c.pos[1];
+    if (params.kernel == kernel_type::laplacian && c.opt.count("sparse") > 0) {  // before the file is read or a GPU touched
+        std::fprintf(stderr, "The laplacian kernel takes dense input: it cannot be combined with --sparse!\n");
+        return EXIT_FAILURE;
+    }
     const auto t0 = std::chrono::steady_clock::now();
     const bool multiclass = c.opt.count("multiclass") > 0;
     params.parse_train_file(c.pos[0], c.opt.count("sparse") > 0, multiclass);
@@ -103,6 +108,7 @@ int train(const cli &c) {
                 std::printf("(gamma*u'*v + coef0)^degree\ngamma: %s\ncoef0: %s\ndegree: %d\n",
                             csvm<T>::shortest(params.gamma).c_str(), csvm<T>::shortest(params.coef0).c_str(), params.degree);
                 break;
+            case kernel_type::laplacian: std::printf("exp(-gamma*|u-v|_1)\ngamma: %s\n", csvm<T>::shortest(params.gamma).c_str()); break;
             default: std::printf("exp(-gamma*|u-v|^2)\ngamma: %s\n", csvm<T>::shortest(params.gamma).c_str()); break;
         }
         std::printf("cost: %s\nepsilon: %s\ninput file (data set): '%s'\noutput file (model): '%s'\n\n",

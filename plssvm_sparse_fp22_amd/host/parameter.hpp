@@ -33,12 +33,14 @@
 
 namespace plssvm::mi355x {
 
-enum class kernel_type { linear = 0, polynomial = 1, rbf = 2 };
+// upstream's numbering; 3 (sigmoid) is not offered
+enum class kernel_type { linear = 0, polynomial = 1, rbf = 2, laplacian = 4 };
 
 inline const char *kernel_name(kernel_type k) {
     switch (k) {
         case kernel_type::linear: return "linear";
         case kernel_type::polynomial: return "polynomial";
+        case kernel_type::laplacian: return "laplacian";
         default: return "rbf";
     }
 }
@@ -48,6 +50,7 @@ inline kernel_type parse_kernel(std::string s) {
     if (s == "linear" || s == "0") return kernel_type::linear;
     if (s == "polynomial" || s == "1") return kernel_type::polynomial;
     if (s == "rbf" || s == "2") return kernel_type::rbf;
+    if (s == "laplacian" || s == "4") return kernel_type::laplacian;
     throw std::invalid_argument("Unrecognized kernel type '" + s + "'!");
 }
 
@@ -473,6 +476,7 @@ struct parameter {
             if (tok == "linear" || tok == "0") kernel = kernel_type::linear;
             else if (tok == "polynomial" || tok == "1") kernel = kernel_type::polynomial;
             else if (tok == "rbf" || tok == "2") kernel = kernel_type::rbf;
+            else if (tok == "laplacian" || tok == "4") kernel = kernel_type::laplacian;
             else throw invalid_file_format_exception("Unrecognized kernel type '" + std::string(value) + "'!");
         } else if (starts("gamma")) {
             gamma = convert_to<real_type>(value);
@@ -618,7 +622,7 @@ struct parameter {
         out += "\n";
         if (kernel == kernel_type::polynomial) {
             out += "degree " + std::to_string(degree) + "\ngamma " + shortest(gamma) + "\ncoef0 " + shortest(coef0) + "\n";
-        } else if (kernel == kernel_type::rbf) {
+        } else if (kernel == kernel_type::rbf || kernel == kernel_type::laplacian) {
             out += "gamma " + shortest(gamma) + "\n";
         }
         out += "nr_class " + std::to_string(K) + "\nlabel";

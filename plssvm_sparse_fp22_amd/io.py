@@ -226,7 +226,7 @@ def _common_header_entry(line, value, header, tn):
     elif line.startswith("kernel_type"):
         tok = value.split()[0] if value.split() else ""
         k = {"linear": "linear", "0": "linear", "polynomial": "polynomial", "1": "polynomial", "rbf": "rbf",
-             "2": "rbf"}.get(tok)
+             "2": "rbf", "laplacian": "laplacian", "4": "laplacian"}.get(tok)
         if k is None:
             raise InvalidFileFormat(f"Unrecognized kernel type '{value}'!")
         header["kernel_type"] = k
@@ -371,12 +371,12 @@ def write_model(path, params, classes, alphas, biases):
     cls = np.searchsorted(classes, labels)
     if np.any(cls >= K) or np.any(classes[np.minimum(cls, K - 1)] != labels):
         raise ValueError("every label must be one of the classes")
-    kernel = {0: "linear", 1: "polynomial", 2: "rbf"}[params.kernel] if not isinstance(params.kernel, str) else \
+    kernel = {0: "linear", 1: "polynomial", 2: "rbf", 4: "laplacian"}[params.kernel] if not isinstance(params.kernel, str) else \
         {"poly": "polynomial"}.get(params.kernel, params.kernel)
     out = [f"svm_type c_svc\nkernel_type {kernel}\n"]
     if kernel == "polynomial":
         out.append(f"degree {int(params.degree)}\ngamma {shortest(params.gamma, dtype)}\ncoef0 {shortest(params.coef0, dtype)}\n")
-    elif kernel == "rbf":
+    elif kernel in ("rbf", "laplacian"):
         out.append(f"gamma {shortest(params.gamma, dtype)}\n")
     out.append(f"nr_class {K}\nlabel {' '.join(shortest(c, dtype) for c in classes)}\ntotal_sv {n}\n")
     out.append(f"nr_sv {' '.join(str(int(c)) for c in np.bincount(cls, minlength=K))}\n")
