@@ -87,6 +87,17 @@ struct kp_vec<float> {
 #ifndef KP_LOAD_NT
 #define KP_LOAD_NT 1
 #endif
+// The slab is written once by the tile kernels and read once by kp_reduce_share_kernel: the tile kernels' slab stores
+// and the reduce's slab loads carry the non-temporal hint as well. -DKP_SLAB_NT=0 builds both plain (A/B in DESIGN.md
+// §3.1.2: the slab pass takes 107 us with the hint and 155 us without)
+#ifndef KP_SLAB_NT
+#define KP_SLAB_NT 1
+#endif
+template <typename T>
+__device__ __forceinline__ void kp_slab_store(T *at, T v) {
+    if constexpr (KP_SLAB_NT != 0) __builtin_nontemporal_store(v, at);
+    else *at = v;
+}
 
 // LDS layout of the epilogue's reduction buffers (element counts): p_I, p_J, n_I, n_J, then row partials
 // [wc][128 rows][16 (+1 pad)] and column partials [wr][128 cols][4 (+1 pad)]
@@ -208,9 +219,9 @@ __device__ __forceinline__ void kp_load_f64(const double *__restrict__ kcache, i
             const double *cp = smem + KP_OFF_PAN + 2 * KP_RHALF + (h * KP_TILE + q) * KP_CSTR;
             double c = (cp[0] + cp[1]) + (cp[2] + cp[3]);
             c += __shfl_xor(c, 1);
-            if (h == 1) partial[wg * KP_REC + KP_TILE + q] = c;  // column sums of the J rows
+            if (h == 1) kp_slab_store(partial + wg * KP_REC + KP_TILE + q, c);  // column sums of the J rows
         }
-        if (h == 0) partial[wg * KP_REC + q] = a;  // row sums of the I rows
+        if (h == 0) kp_slab_store(partial + wg * KP_REC + q, a);  // row sums of the I rows
     } else {
         double kv[16][4];  // decoded once; the record's registers die here
 #pragma unroll
@@ -260,9 +271,9 @@ __device__ __forceinline__ void kp_load_f64(const double *__restrict__ kcache, i
                 const double *cp = smem + KP_OFF_PAN + 2 * KP_RHALF + (h * KP_TILE + q) * KP_CSTR;
                 double cc = (cp[0] + cp[1]) + (cp[2] + cp[3]);
                 cc += __shfl_xor(cc, 1);
-                if (h == 1) slab[wg * KP_REC + KP_TILE + q] = cc;  // column sums of the J rows
+                if (h == 1) kp_slab_store(slab + wg * KP_REC + KP_TILE + q, cc);  // column sums of the J rows
             }
-            if (h == 0) slab[wg * KP_REC + q] = a;  // row sums of the I rows
+            if (h == 0) kp_slab_store(slab + wg * KP_REC + q, a);  // row sums of the I rows
             if (cn < 0) break;
             c = cn;
         }
@@ -628,9 +639,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_wav
             const T *cp = smem + OFF_PAN + 2 * RHALF + (h * KP_TILE + q) * CSTR;
             T c = (cp[0] + cp[1]) + (cp[2] + cp[3]);
             c += __shfl_xor(c, 1);
-            if (h == 1) partial[wg * KP_REC + KP_TILE + q] = c;  // column sums of the J rows
+            if (h == 1) kp_slab_store(partial + wg * KP_REC + KP_TILE + q, c);  // column sums of the J rows
         }
-        if (h == 0) partial[wg * KP_REC + q] = a;  // row sums of the I rows
+        if (h == 0) kp_slab_store(partial + wg * KP_REC + q, a);  // row sums of the I rows
     } else {
         // The same epilogue in two steps. First the kernel function, once, in place: the call and its arguments are
         // the single-vector branch's, so the values are its values (KP_LOAD: they are the record). Then one turn per
@@ -708,79 +719,156 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kp_mode_wav
                 const T *cp = smem + OFF_PAN + 2 * RHALF + (h * KP_TILE + q) * CSTR;
                 T cc = (cp[0] + cp[1]) + (cp[2] + cp[3]);
                 cc += __shfl_xor(cc, 1);
-                if (h == 1) slab[wg * KP_REC + KP_TILE + q] = cc;  // column sums of the J rows
+                if (h == 1) kp_slab_store(slab + wg * KP_REC + KP_TILE + q, cc);  // column sums of the J rows
             }
-            if (h == 0) slab[wg * KP_REC + q] = a;  // row sums of the I rows
+            if (h == 0) kp_slab_store(slab + wg * KP_REC + q, a);  // row sums of the I rows
             if (cn < 0) break;
             c = cn;
         }
     }
 }
 
-// Slab values of row i (row block Ib, offset q) for the column blocks c of column super-block CS, in c
-// order: tile (Ib, c)'s row sums when c <= Ib, tile (c, Ib)'s column sums when c > Ib. base = the first
-// record of the super-block holding those tiles (kp_tile_offsets' table); tiles inside a super-block are
-// numbered row-major (a diagonal one: its lower triangle, ta (ta + 1) / 2 + tb).
-template <typename T>
-__device__ __forceinline__ void kp_sb_values(const T *__restrict__ partial, int64_t Ib, int64_t q, int64_t CS,
-                                             int64_t nb, int64_t base, T *v, int cnt) {
-    const int64_t RS = Ib / KP_SUPER;
-    for (int u = 0; u < cnt; ++u) {
-        const int64_t c = CS * KP_SUPER + u;
-        const int64_t I = c <= Ib ? Ib : c, J = c <= Ib ? c : Ib;
-        const int64_t SI = c <= Ib ? RS : CS, SJ = c <= Ib ? CS : RS;
-        const int64_t ta = I - SI * KP_SUPER, tb = J - SJ * KP_SUPER;
-        const int64_t local = SI == SJ ? ta * (ta + 1) / 2 + tb : ta * min<int64_t>(KP_SUPER, nb - SJ * KP_SUPER) + tb;
-        v[u] = partial[(base + local) * KP_REC + (c <= Ib ? 0 : KP_TILE) + q];
-    }
-}
-
-
-// raw[i] = sum of the slab values of the super-blocks [s0, s1) (a rank's share, or the whole triangle): the
-// column super-blocks of a row are dealt to the 16 waves of a block (64 rows per block, lanes = rows:
-// coalesced) and the 16 partial sums are added in wave order — a fixed order, deterministic; the critical
-// path per thread is 1/16 of the row (one thread per row is latency-bound)
+// raw[i] = sum of the slab values of the super-blocks [s0, s1) (a rank's share, or the whole triangle), in a fixed
+// order: sixteen chains g = 0 .. 15, each from 0; chain g walks the column super-blocks CS = g, g + 16, ... in
+// ascending order (skipping those outside [s0, s1)) and inside one the column blocks c = 8 CS + u, u = 0 .. cnt - 1,
+// adding one value at a time — tile (Ib, c)'s row sum for c <= Ib, tile (c, Ib)'s column sum for c > Ib; then the
+// chains are added in g order. That order is the interface (tests/test_gpu_kp_reduce_order.py pins it bitwise); the
+// shape below only decides how fast the slab arrives:
+//   * one block per row block Ib, a lane holds rows 2 lane and 2 lane + 1 of it, so one wave instruction reads a
+//     whole half record (128 row sums or 128 column sums): 16 bytes per lane, 1 KiB contiguous in fp64;
+//   * KP_RED_WAVES waves per block, wave w carries the chains w, w + KP_RED_WAVES, ...: with 4 waves a block is 256
+//     threads and every block of the flagship's grid (782) is resident at once, so there is no last, nearly empty
+//     round;
+//   * a step is one super-block of one chain (8 loads); the loads of KP_RED_BATCH steps (of different chains) are
+//     issued together, then their adds follow. Nothing is carried in registers from one batch to the next: a loop
+//     that kept the next step's loads in flight under the adds (two buffers) spilled at 128 VGPRs in fp64.
+// Every index but the lane's offset is wave-uniform. Rows past m are read (the records are whole) but not stored.
 constexpr int KP_RED_G = 16;
+#ifndef KP_RED_WAVES
+#define KP_RED_WAVES 4
+#endif
+#ifndef KP_RED_BATCH
+#define KP_RED_BATCH 2
+#endif
+static_assert(KP_RED_G % KP_RED_WAVES == 0 && KP_RED_WAVES >= 1 && KP_RED_WAVES <= KP_RED_G, "waves must divide the 16 chains");
 template <typename T>
-__global__ __launch_bounds__(64 * KP_RED_G) void kp_reduce_share_kernel(const T *__restrict__ partial, int64_t nb,
-                                                                        int64_t m, int64_t s0, int64_t s1,
-                                                                        const int32_t *__restrict__ wg_off,
-                                                                        T *__restrict__ raw,
-                                                                        const cg_scalars<T> *__restrict__ status) {
+using kp_row2 = T __attribute__((ext_vector_type(2)));
+
+// One step: the values of row block Ib in column super-block CS, i.e. the column blocks c = 8 CS + u, u < cnt. With
+// t = Ib % 8 and base = the first record of the super-block holding those tiles (kp_tile_offsets' table; tiles inside
+// a super-block are numbered row-major, a diagonal one: its lower triangle, ta (ta + 1) / 2 + tb):
+//   * CS below the row's own super-block RS: tile (Ib, c), record base + 8 t + u, its row sums;
+//   * CS above RS: tile (c, Ib), record base + 8 u + t, its column sums (both super-block columns are full ones);
+//   * CS = RS, the diagonal super-block: u <= t is tile (Ib, c), record base + t (t + 1) / 2 + u, row sums; u > t is
+//     tile (c, Ib), record base + u (u + 1) / 2 + t, column sums.
+// Off the diagonal value u therefore sits at byte off0 + u stride of the slab (stride: one record, or eight): no
+// compare between the loads. The one diagonal step of a row block picks per u between its row part (off0, stride one
+// record) and its column part (col0 + u (u + 1) / 2 records). All of it is wave-uniform.
+struct kp_red_step {
+    int cnt;  // column blocks of the step's super-block, 0: nothing to add (not the rank's, or past the last)
+    int t;    // >= 0: the diagonal step, the last u that reads row sums; -1: off the diagonal
+    int64_t off0, stride, col0;  // bytes
+};
+
+// at least 4 waves per SIMD (<= 128 VGPRs): with 4-wave blocks that is at least 4 blocks per CU
+template <typename T>
+__global__ __launch_bounds__(64 * KP_RED_WAVES) __attribute__((amdgpu_waves_per_eu(4))) void kp_reduce_share_kernel(
+    const T *__restrict__ partial, int64_t nb, int64_t m, int64_t s0, int64_t s1, const int32_t *__restrict__ wg_off,
+    T *__restrict__ raw, const cg_scalars<T> *__restrict__ status) {
     if (status != nullptr && status->converged) return;
-    __shared__ T red[KP_RED_G][64];
-    const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int64_t i = (int64_t) blockIdx.x * 64 + lane;
-    const int64_t ns = (nb + KP_SUPER - 1) / KP_SUPER;
-    const int64_t Ib = __builtin_amdgcn_readfirstlane((int) (((int64_t) blockIdx.x * 64) / KP_TILE));
-    T s = 0;
-    if (i < m) {
-        const int64_t q = i % KP_TILE, RS = Ib / KP_SUPER;
-        // column super-blocks dealt round-robin to the waves: a rank's owned super-blocks of a row (often a
-        // short run of CS) spread over the waves instead of landing in one
-        for (int64_t CS = g; CS < ns; CS += KP_RED_G) {
+    constexpr int W = KP_RED_WAVES, CPW = KP_RED_G / W;  // chains per wave
+    constexpr int B = CPW < KP_RED_BATCH ? CPW : KP_RED_BATCH;  // steps whose loads are issued together
+    static_assert(CPW % B == 0, "the batch must divide the wave's chains");
+    using row2 = kp_row2<T>;
+    __shared__ row2 red[KP_RED_G][64];
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+    const int64_t Ib = blockIdx.x;
+    const int64_t ns = (nb + KP_SUPER - 1) / KP_SUPER, RS = Ib / KP_SUPER;
+    const int t = (int) (Ib % KP_SUPER);
+    const int64_t turns = (ns + KP_RED_G - 1) / KP_RED_G;
+
+    // the wave's chain k (g = w + W k) in turn `turn`: the chain's super-block number `turn`
+    auto step = [&](int64_t turn, int k) -> kp_red_step {
+        const int64_t CS = (w + W * k) + KP_RED_G * turn;
+        kp_red_step st{ 0, -1, 0, 0, 0 };
+        if (CS < ns) {
             const int64_t sb = (RS >= CS) ? tri_index(RS, CS) : tri_index(CS, RS);
-            if (sb < s0 || sb >= s1) continue;
-            const int64_t base = wg_off[sb - s0];
-            const int cnt = (int) min<int64_t>(KP_SUPER, nb - CS * KP_SUPER);
-            T v[KP_SUPER];
-            if (cnt == KP_SUPER) {
-                kp_sb_values(partial, Ib, q, CS, nb, base, v, KP_SUPER);
+            if (sb >= s0 && sb < s1) {
+                const int64_t base = wg_off[sb - s0];
+                const int64_t col0 = ((base + t) * KP_REC + KP_TILE) * (int64_t) sizeof(T);
+                st.cnt = (int) min<int64_t>(KP_SUPER, nb - CS * KP_SUPER);
+                st.t = CS == RS ? t : -1;
+                st.off0 = CS > RS ? col0 : (base + (CS == RS ? t * (t + 1) / 2 : t * KP_SUPER)) * KP_REC * (int64_t) sizeof(T);
+                st.stride = (CS > RS ? KP_SUPER : 1) * KP_REC * (int64_t) sizeof(T);
+                st.col0 = col0;
+            }
+        }
+        return st;
+    };
+    // A full step off the diagonal (all but a row block's one diagonal step and the ragged last super-block): eight
+    // loads from one scalar base, the multiples of the stride in the lane's 32-bit offset (at most 112 KiB), nothing
+    // else between them; then the eight adds.
+    const char *slab = reinterpret_cast<const char *>(partial);
+    const uint32_t lane_off = (uint32_t) lane * (uint32_t) sizeof(row2);
+    auto full = [](const kp_red_step &st) { return st.t < 0 && st.cnt == KP_SUPER; };
+    auto fetch = [&](const kp_red_step &st, row2 *v) {
+        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t) st.off0);
+        const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t) ((uint64_t) st.off0 >> 32));
+        const uint32_t stride = __builtin_amdgcn_readfirstlane((uint32_t) st.stride);
+        const char *base = slab + (((uint64_t) hi << 32) | lo);
 #pragma unroll
-                for (int u = 0; u < KP_SUPER; ++u) s += v[u];
-            } else {
-                kp_sb_values(partial, Ib, q, CS, nb, base, v, cnt);
-                for (int u = 0; u < cnt; ++u) s += v[u];
+        for (int u = 0; u < KP_SUPER; ++u) {
+            const row2 *at = reinterpret_cast<const row2 *>(base + (lane_off + (uint32_t) u * stride));
+            v[u] = KP_SLAB_NT ? __builtin_nontemporal_load(at) : *at;
+        }
+    };
+    // The other steps, at most two per chain: one value at a time (a loop that is not unrolled keeps this rare path
+    // out of the registers and the schedule of the one above). Nothing to do for cnt = 0.
+    auto slow = [&](row2 &s, const kp_red_step &st) {
+#pragma nounroll
+        for (int u = 0; u < st.cnt; ++u) {
+            const int64_t off = (st.t < 0 || u <= st.t) ? st.off0 + u * st.stride
+                                                        : st.col0 + (int64_t) (u * (u + 1) / 2) * KP_REC * (int64_t) sizeof(T);
+            const row2 *at = reinterpret_cast<const row2 *>(slab + off) + lane;
+            s += KP_SLAB_NT ? __builtin_nontemporal_load(at) : *at;
+        }
+    };
+
+    row2 acc[CPW];
+#pragma unroll
+    for (int k = 0; k < CPW; ++k) acc[k] = row2{ T(0), T(0) };
+    for (int64_t turn = 0; turn < turns; ++turn) {
+#pragma unroll
+        for (int k0 = 0; k0 < CPW; k0 += B) {  // unrolled: the chains k0 + b are constants
+            kp_red_step st[B];
+            row2 v[B][KP_SUPER];
+#pragma unroll
+            for (int b = 0; b < B; ++b) st[b] = step(turn, k0 + b);
+#pragma unroll
+            for (int b = 0; b < B; ++b)
+                if (full(st[b])) fetch(st[b], v[b]);
+#pragma unroll
+            for (int b = 0; b < B; ++b) {  // both rows of the lane: one add each per value, in u order
+                if (full(st[b])) {
+#pragma unroll
+                    for (int u = 0; u < KP_SUPER; ++u) acc[k0 + b] += v[b][u];
+                } else {
+                    slow(acc[k0 + b], st[b]);
+                }
             }
         }
     }
-    red[g][lane] = s;
+#pragma unroll
+    for (int k = 0; k < CPW; ++k) red[w + W * k][lane] = acc[k];
     __syncthreads();
-    if (g == 0 && i < m) {
-        T a = red[0][lane];
+    if (w == 0) {
+        row2 a = red[0][lane];
 #pragma unroll
         for (int h = 1; h < KP_RED_G; ++h) a += red[h][lane];
-        raw[i] = a;
+        const int64_t i = Ib * KP_TILE + 2 * lane;
+        if (i < m) raw[i] = a[0];
+        if (i + 1 < m) raw[i + 1] = a[1];
     }
 }
 
@@ -871,15 +959,16 @@ void launch_kp_tiles_multi(const kp_geom<T> &g, const T *p, int64_t pstride, T *
 #undef KP_LAUNCH
 }
 
-// Both the whole triangle and a rank's share use the wave-split reduction (16 waves per 64 rows, each a
-// range of column super-blocks, partial sums added in wave order): one thread per row walking all nb
-// records (round 1's kp_reduce_kernel) was latency-bound — 0.43 ms for config 2's 627 MB slab.
+// Both the whole triangle and a rank's share use the chain-split reduction (one block per row block of 128 rows,
+// 16 chains of column super-blocks dealt to its waves, the chains added in order): one thread per row walking all
+// nb records (round 1's kp_reduce_kernel) was latency-bound — 0.43 ms for config 2's 627 MB slab.
 template <typename T>
 void launch_kp_reduce(const T *partial, int64_t nb, int64_t m, int64_t s0, int64_t s1, const int32_t *wg_off, T *raw,
                       const cg_scalars<T> *status, hipStream_t s) {
     if (m <= 0) return;
-    hipLaunchKernelGGL(kp_reduce_share_kernel<T>, dim3((unsigned) ceil_div(m, 64)), dim3(64 * KP_RED_G), 0, s,
-                       partial, nb, m, s0, s1, wg_off, raw, status);
+    if (ceil_div(m, (int64_t) KP_TILE) > nb) throw mi_error(-1, "the slab pass needs a row block for every row");
+    hipLaunchKernelGGL(kp_reduce_share_kernel<T>, dim3((unsigned) ceil_div(m, (int64_t) KP_TILE)), dim3(64 * KP_RED_WAVES), 0,
+                       s, partial, nb, m, s0, s1, wg_off, raw, status);
     MI_LAUNCH_CHECK();
 }
 
