@@ -11,7 +11,11 @@ with np.array_equal.
 Shapes: (130, 5) two tile rows, a diagonal and an off-diagonal tile, d below one chunk; (300, 37) three ragged tile
 rows, d off the chunk depth; (385, 256) m = exactly three tiles; (386, 256) one row more. Data: uniform [-1, 1], the
 same plus 100 (L1 differences do not cancel: no shift is needed), and gamma = 1 at (300, 37), where most values
-underflow towards 0 and stored fp64 tiles stay raw.
+underflow towards 0 and stored fp64 tiles stay raw. The edges: (2, 1) one row, one feature; (3, 5); (129, 16) m = exactly
+one tile and d exactly one chunk of 16; (130, 17) one row and one feature more; (1100, 3) nine tile rows, i.e. two rows
+of super-blocks on a single rank; (300, 37) once more with a signed vector, whose sum cancels. At m = 1100, d = 8 a
+memory budget of 22 of the 45 tiles makes every K.p one launch over the stored prefix and one Laplacian KP_COMPUTE launch
+over the rest.
 """
 import ctypes
 import functools
@@ -31,7 +35,9 @@ COST = 1.0
 # (n, d, offset, gamma; None: 1 / d)
 KP_CASES = [(130, 5, 0.0, None), (130, 5, 100.0, None), (300, 37, 0.0, None), (300, 37, 100.0, None),
             (385, 256, 0.0, None), (385, 256, 100.0, None), (386, 256, 0.0, None), (386, 256, 100.0, None),
-            (300, 37, 0.0, 1.0)]
+            (300, 37, 0.0, 1.0),
+            (2, 1, 0.0, None), (3, 5, 0.0, None), (129, 16, 0.0, None), (130, 17, 0.0, None), (1100, 3, 0.0, None),
+            (300, 37, 0.0, None, "signed")]  # a fifth entry: the vector is uniform(-1, 2), not [1, 2]
 
 
 def l1_kernel(X, Z, gamma):
@@ -66,9 +72,9 @@ def make_svm(X, gamma, dtype, labels=None, epsilon=1e-3, **kw):
     return pm.CSVM(p, **kw)
 
 
-def vectors(m, dtype, count=2, seed=3):
+def vectors(m, dtype, count=2, seed=3, signed=False):
     rng = np.random.default_rng(seed + m)
-    return [rng.uniform(1.0, 2.0, m).astype(dtype) for _ in range(count)]
+    return [rng.uniform(-1.0 if signed else 1.0, 2.0, m).astype(dtype) for _ in range(count)]
 
 
 def assert_close(got, want, dtype, what):
@@ -80,9 +86,10 @@ def assert_close(got, want, dtype, what):
 
 # ---- K.p and q against numpy ---------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("case", KP_CASES, ids=lambda c: f"{c[0]}x{c[1]}+{c[2]:g}-g{c[3]}")
+@pytest.mark.parametrize("case", KP_CASES, ids=lambda c: f"{c[0]}x{c[1]}+{c[2]:g}-g{c[3]}" + "".join(f"-{x}" for x in c[4:]))
 def test_kp_and_q_against_numpy(case, dtype):
-    n, d, offset, gamma = case
+    n, d, offset, gamma = case[:4]
+    signed = "signed" in case[4:]
     X, g, K = kp_case(n, d, offset, gamma, dtype)
     m = n - 1
     with make_svm(X, g, dtype) as svm:
@@ -93,7 +100,8 @@ def test_kp_and_q_against_numpy(case, dtype):
         q_ref, qa_ref = K[:m, m], K[m, m] + 1.0 / COST
         assert_close(q, q_ref, dtype, "q")
         assert abs(float(svm.QA_cost) - qa_ref) <= KP_TOL[dtype] * qa_ref
-        p = vectors(m, dtype, 1)[0]
+        p = vectors(m, dtype, 1, signed=signed)[0]
+        assert not signed or ((p < 0).any() and (p > 0).any())
         p64 = p.astype(np.float64)
         kp_ref = K[:m, :m] @ p64
         assert_close(svm.kp_part(p, "kernel"), kp_ref, dtype, "kp_part")
@@ -140,6 +148,44 @@ def test_cache_invariance_bitwise(dtype, pack, gamma):
         assert info["kp_cache_packed_tiles"] >= 1, info  # values within a few binades of 1
     if pack == "wide":
         assert info["kp_cache_narrow_tiles"] == 0, info
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_partial_cache_bitwise(dtype, monkeypatch):
+    """m = 1100, d = 8: 45 tiles, a budget for 22 raw records and a half (test_gpu_kp_reduce_order.test_partial_cache's).
+    Tiles [0, 22) are stored by the filling K.p and streamed afterwards, tiles [22, 45) are formed by a Laplacian
+    KP_COMPUTE launch each time (launch_kp_tiles, launch_kp_tiles_multi): the same bits as with no cache at all, which
+    is itself within the bar of numpy."""
+    n, d, R, want_tiles = 1101, 8, 3, 22
+    X, g, K = kp_case(n, d, 0.0, None, dtype)
+    m = n - 1
+    P = np.stack(vectors(m, dtype, R, seed=29, signed=True))
+    q_ref, qa_ref = K[:m, m], K[m, m] + 1.0 / COST
+
+    def run(svm):
+        svm.setup_data_on_device()
+        svm.generate_q()
+        first = svm.run_device_kernel(None, np.zeros(m, dtype=dtype), P[0], 1.0).copy()
+        second = svm.run_device_kernel(None, np.zeros(m, dtype=dtype), P[0], 1.0).copy()
+        multi = svm.run_device_kernel_multi(None, np.zeros((R, m), dtype=dtype), P, 1.0).copy()
+        return first, second, multi, svm.info()
+
+    with make_svm(X, g, dtype, kp_cache=False) as svm:
+        want, again, want_multi, info = run(svm)
+        assert info["kp_cache_tiles"] == 0
+    assert np.array_equal(again, want) and np.array_equal(want_multi[0], want)
+    for c in range(R):
+        p64 = P[c].astype(np.float64)
+        ref = K[:m, :m] @ p64 + (qa_ref - q_ref) * p64.sum() - q_ref @ p64 + p64 / COST
+        assert_close(want_multi[c], ref, dtype, f"no cache, vector {c}")
+    rec = 128 * 128 * np.dtype(dtype).itemsize
+    monkeypatch.setenv("PLSSVM_MI_MEM_BUDGET", str(want_tiles * rec + rec // 2))
+    with make_svm(X, g, dtype, kp_cache=True) as svm:
+        fill, stream, multi, info = run(svm)
+    assert info["kp_cache_tiles"] == want_tiles, info
+    assert np.array_equal(fill, want), np.abs(fill - want).max()
+    assert np.array_equal(stream, want), np.abs(stream - want).max()
+    assert np.array_equal(multi, want_multi), np.abs(multi - want_multi).max()
 
 
 # ---- batched K.p and one-vs-all training ------------------------------------------------------------------------------
@@ -257,7 +303,10 @@ def test_learn_against_numpy_cg(dtype):
     gives no "few tens of iterations" at which alpha is comparable at 1e-9. epsilon is set so that the solve ends after
     three iterations, where float64 arithmetic is a factor 17 inside the alpha bar: 1.45e-4 in fp64 (eps^2 = 2.1e-8 lies
     a factor 1.8 under iteration 2 and 1.9 over iteration 3; the trace is good to 2e-13 there, so the count does not
-    hang on rounding) and 1e-3 in fp32 (two iterations: the three trace entries the fp32 bar covers)."""
+    hang on rounding) and 1e-3 in fp32 (two iterations: the three trace entries the fp32 bar covers).
+
+    On an MI355X, as written: fp64 three iterations, trace within 2.1e-13, alpha within 5.3e-10 of max|alpha|; fp32 two
+    iterations, trace within 3.4e-5, alpha within 7.3e-4."""
     n, d = 400, 16
     X, y = datagen.blobs(n, d, seed=6, dtype=dtype, cluster_std=2.0)
     g = rounded_gamma(d, dtype)
