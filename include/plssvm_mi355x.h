@@ -303,6 +303,28 @@ PLSSVM_MI_API int plssvm_mi_solve_cg_multi(plssvm_mi_ctx *ctx, const void *B, in
 PLSSVM_MI_API int plssvm_mi_learn_multi(plssvm_mi_ctx *ctx, const void *Y, int64_t nclass, int64_t ldy, int64_t imax,
                                         double eps, void *alpha_out, double *bias_out, double *delta_trace,
                                         int64_t *iters);
+/* Point weights (build-defined; LIBSVM's -wi as a vector): point i is trained at cost C * s_i. In the LS-SVM system
+ * only the diagonal changes: row i's 1/C becomes (1/C) * (1/s_i) and QA_cost = k(x_m, x_m) + (1/C) * (1/s_m), both
+ * reciprocals and their product rounded in the real type, so s_i = 1 everywhere gives bitwise the unweighted results.
+ * s: n reals of the context's type (the last point included), all finite and > 0; NULL clears the weights. They apply
+ * to plssvm_mi_kp, _kp_multi, _solve_cg*, _cg_begin / _cg_step, _learn and _learn_multi (every class the same
+ * weights) until they are cleared; any plssvm_mi_setup_* clears them, plssvm_mi_set_cost does not. With a q in place
+ * the context's QA_cost is formed anew as above (a value from plssvm_mi_set_qa_cost is replaced). Before a setup, or
+ * with an entry that is not finite and > 0: PLSSVM_MI_ERR_ARG, the context's weights unchanged. In a group every
+ * rank's context gets the same call. */
+PLSSVM_MI_API int plssvm_mi_set_point_weights(plssvm_mi_ctx *ctx, const void *s);
+/* Lanes that differ in their diagonal: lane k is plssvm_mi_learn on the labels Y[k] (rows ldy >= n apart) at cost
+ * costs[k] (costs NULL: the context's cost) with the point weights S[k] (rows lds >= n apart; lds == 0: S is one row
+ * that every lane shares; S NULL: the context's weights, if any). A cost grid is nlane copies of one label row with
+ * nlane costs; one-vs-all with weighted positives is plssvm_mi_learn_multi's Y with one weight row per class. The
+ * lanes share each pass over the kernel matrix exactly where plssvm_mi_learn_multi's classes do (and run one after
+ * another elsewhere); lane k is BITWISE plssvm_mi_set_cost(costs[k]), plssvm_mi_set_point_weights(S[k]),
+ * plssvm_mi_learn(Y[k]). Outputs as plssvm_mi_learn_multi's. The context's own cost and weights are what they were
+ * when the call returns. nlane < 1, ldy < n, 0 < lds < n, a cost or a weight that is not finite and > 0:
+ * PLSSVM_MI_ERR_ARG. plssvm_mi_learn_multi is this call with costs = S = NULL. */
+PLSSVM_MI_API int plssvm_mi_learn_lanes(plssvm_mi_ctx *ctx, const void *Y, int64_t nlane, int64_t ldy, const double *costs,
+                                        const void *S, int64_t lds, int64_t imax, double eps, void *alpha_out,
+                                        double *bias_out, double *delta_trace, int64_t *iters);
 /* Timing hook: plssvm_mi_time_kp's K·p time for the product with nrhs resident vectors (in groups of the width; one at
  * a time where nothing is batched), averaged over `reps` products, measured with hipEvents on the context's stream. */
 PLSSVM_MI_API int plssvm_mi_time_kp_multi(plssvm_mi_ctx *ctx, int64_t nrhs, int reps, double *ms_per_kp);

@@ -185,6 +185,8 @@ class device_group {
 
     // f(rank, ctx) -> PLSSVM_MI_* code, on every rank's thread at once. The first failure aborts the group and
     // is rethrown here as group_error (code, rank, that context's message).
+    // plssvm_mi_set_point_weights and plssvm_mi_learn_lanes are per-rank calls like every other: each rank's context
+    // gets the same weights, costs and labels (csvm<T>::set_class_weights / learn_costs in host/csvm.hpp do so).
     void run(const std::function<int(int, plssvm_mi_ctx *&)> &f) {
         if (dead_) throw group_error(PLSSVM_MI_ERR_STATE, 0, "the device group was aborted by an earlier failure");
         const int world = size();

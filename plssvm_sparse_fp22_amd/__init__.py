@@ -25,7 +25,8 @@ from . import io as _io
 from .io import parse_libsvm, parse_model, read_binary, write_binary, write_model
 
 __all__ = ["Parameter", "CSVM", "BackendError", "parse_libsvm", "parse_model", "read_binary", "write_binary",
-           "device_count", "unique_id", "partition", "torch_exchange", "one_vs_all"]
+           "device_count", "unique_id", "partition", "torch_exchange", "one_vs_all", "class_point_weights",
+           "one_vs_all_weights"]
 
 
 def device_count() -> int:
@@ -107,6 +108,47 @@ def one_vs_all(labels, dtype=np.float64):
     return classes, np.ascontiguousarray(Y)
 
 
+def _check_class_weight(class_weight):
+    """{label: weight} with finite weights > 0, or None."""
+    if class_weight is None:
+        return None
+    if not isinstance(class_weight, dict) or not class_weight:
+        raise ValueError("class_weight must be a non-empty {label: weight} dict")
+    for lab, w in class_weight.items():
+        if not (np.isfinite(w) and w > 0):
+            raise ValueError(f"class_weight: the weight of label {lab!r} must be a finite number > 0, not {w!r}")
+    return dict(class_weight)
+
+
+def class_point_weights(labels, class_weight, dtype=np.float64):
+    """Point weights s [n] of a {label: weight} dict (LIBSVM's -wi): s_i = the weight of point i's label, 1 for a label
+    the dict does not name. A label in the dict that the data lacks is a ValueError."""
+    cw = _check_class_weight(class_weight)
+    labels = np.asarray(labels)
+    s = np.ones(labels.shape[0], dtype=dtype)
+    for lab, w in cw.items():
+        hit = labels == lab
+        if not hit.any():
+            raise ValueError(f"class_weight names the label {lab!r}, which the data does not have")
+        s[hit] = w
+    return s
+
+
+def one_vs_all_weights(labels, class_weight, dtype=np.float64):
+    """The weight rows S [K][n] of one-vs-all training with weighted positives: row c weighs the points of class c by
+    class_weight[c] and every other point by 1 (classes the dict does not name: all 1)."""
+    cw = _check_class_weight(class_weight)
+    classes, _ = one_vs_all(labels, dtype)
+    labels = np.asarray(labels)
+    S = np.ones((classes.size, labels.shape[0]), dtype=dtype)
+    for lab, w in cw.items():
+        hit = np.flatnonzero(classes == lab)
+        if hit.size == 0:
+            raise ValueError(f"class_weight names the label {lab!r}, which the data does not have")
+        S[hit[0], labels == lab] = w
+    return np.ascontiguousarray(S)
+
+
 def _rows(a, dtype, m, what):
     """[R][ld] row-major matrix of the real type with ld >= m (a 1-D vector counts as one row)."""
     a = np.ascontiguousarray(np.atleast_2d(a), dtype=dtype)
@@ -125,9 +167,12 @@ class Parameter:
     """plssvm::parameter<T> subset used by the hot path."""
 
     def __init__(self, kernel="linear", degree=3, gamma=0.0, coef0=0.0, cost=1.0, epsilon=1e-3,
-                 real_type=np.float64, print_info=False):
+                 real_type=np.float64, print_info=False, class_weight=None):
         if kernel not in KERNELS:
             raise ValueError(f"Unknown kernel type {kernel!r}")
+        # {label: weight}: learn() trains the points of `label` at cost C * weight (binary labels; learn_multi takes
+        # its own class_weight)
+        self.class_weight = _check_class_weight(class_weight)
         self.kernel = kernel
         self.degree = int(degree)
         self.gamma = gamma
@@ -167,6 +212,14 @@ class Parameter:
         if self.gamma == 0:  # parameter.cpp:150-152
             self.gamma = float(self.real_type.type(1) / self.real_type.type(d))
         return self
+
+    def point_weights(self):
+        """The point weights of class_weight on this parameter's labels (None without class_weight)."""
+        if self.class_weight is None:
+            return None
+        if self.labels is None:
+            raise ValueError("class_weight needs labels")
+        return class_point_weights(self.labels, self.class_weight, self.real_type)
 
     @property
     def num_features(self):
@@ -251,6 +304,7 @@ class CSVM:
         self.iters_multi = None
         self.traces = None
         self._on_device = False
+        self._cw_applied = False  # the context's weights are those of Parameter.class_weight (learn / learn_costs)
 
     @staticmethod
     def _exchange_cb(exchange, world_size):
@@ -317,6 +371,7 @@ class CSVM:
             val = np.ascontiguousarray(val, dtype=np.uint32 if p.val_fmt == _abi.VAL_FP22 else self.dtype)
             self._check(L.plssvm_mi_setup_coo(self._ctx, _ptr(row), _ptr(col), _ptr(val), p.val_fmt, row.size, n, d))
         self._on_device = True
+        self._cw_applied = False  # a setup clears the context's weights
 
     def generate_q(self):
         q = np.zeros(max(self.m, 1), dtype=self.dtype)
@@ -327,6 +382,27 @@ class CSVM:
 
     def set_cost(self, cost):
         self._check(_abi.lib().plssvm_mi_set_cost(self._ctx, float(cost)))
+
+    def set_point_weights(self, s):
+        """Point i is trained at cost C * s[i] (s: n finite reals > 0, the last point included; None clears them). They
+        hold for every later K.p, CG solve and learn of this context until cleared or the next setup."""
+        if not self._on_device:
+            self.setup_data_on_device()
+        if s is not None:
+            s = np.ascontiguousarray(s, dtype=self.dtype)
+            if s.shape != (self.num_data_points,):
+                raise ValueError(f"the point weights must have {self.num_data_points} entries")
+        self._check(_abi.lib().plssvm_mi_set_point_weights(self._ctx, _ptr(s)))
+        self._cw_applied = False
+
+    def _apply_class_weight(self, s):
+        """The weights of Parameter.class_weight (s; None: none) for a learn: set, or — where an earlier learn applied
+        some — cleared. Weights the caller set with set_point_weights stay."""
+        if s is not None:
+            self.set_point_weights(s)
+            self._cw_applied = True
+        elif self._cw_applied:
+            self.set_point_weights(None)
 
     def set_QA_cost(self, qa):
         self._check(_abi.lib().plssvm_mi_set_qa_cost(self._ctx, float(qa)))
@@ -366,8 +442,10 @@ class CSVM:
         """csvm<T>::learn(): setup, q, QA_cost, CG with imax = num_features, bias, alpha[m] = -sum."""
         if self.params.labels is None:
             raise ValueError("No labels given for training! Maybe the data is only usable for prediction?")
+        s = self.params.point_weights()  # class_weight (checked before the device is touched)
         if not self._on_device:
             self.setup_data_on_device()
+        self._apply_class_weight(s)
         y = np.ascontiguousarray(self.params.labels, dtype=self.dtype)
         alpha = np.zeros(self.num_data_points, dtype=self.dtype)
         bias = ctypes.c_double()
@@ -410,10 +488,56 @@ class CSVM:
         self.traces = [trace[c, : it[c] + 1].copy() for c in range(R)]
         return X[:, : self.m]
 
-    def learn_multi(self, labels=None, imax=-1):
+    def _learn_lanes(self, Y, costs, S, imax):
+        """plssvm_mi_learn_lanes on Y [K][n]: costs [K] or None, S [K][n] / [n] (one row for all) or None."""
+        K, n = Y.shape
+        im = self.num_features if imax < 0 else imax
+        alphas = np.zeros((K, n), dtype=self.dtype)
+        biases = np.zeros(K, dtype=np.float64)
+        trace = np.full((K, im + 1), np.nan)
+        it = np.zeros(K, dtype=np.int64)
+        cc = None if costs is None else np.ascontiguousarray(costs, dtype=np.float64)
+        SS = None if S is None else np.ascontiguousarray(S, dtype=self.dtype)
+        if cc is not None and cc.shape != (K,):
+            raise ValueError(f"costs must have {K} entries")
+        if SS is not None and SS.shape not in ((K, n), (n,)):
+            raise ValueError(f"the weights must be [{K}][{n}] or one row of {n}")
+        lds = 0 if SS is None or SS.ndim == 1 else SS.shape[1]
+        self._check(_abi.lib().plssvm_mi_learn_lanes(self._ctx, _ptr(Y), K, n, _ptr(cc), _ptr(SS), lds, im,
+                                                     float(self.params.epsilon), _ptr(alphas), _ptr(biases),
+                                                     _ptr(trace), _ptr(it)))
+        self.alphas = alphas
+        self.biases = biases.astype(self.dtype)
+        self.iters_multi = it
+        self.traces = [trace[c, : it[c] + 1].copy() for c in range(K)]
+        return self
+
+    def learn_costs(self, costs, imax=-1):
+        """learn() at every cost of `costs` (a search over C): the K systems share every kernel value and differ only in
+        their diagonal, so where learn_multi's classes share a pass over the kernel matrix these do too. Row k of alphas
+        [K][n], biases [K], iters_multi, traces is bitwise set_cost(costs[k]); learn(). The context's cost stays."""
+        if self.params.labels is None:
+            raise ValueError("No labels given for training! Maybe the data is only usable for prediction?")
+        costs = np.atleast_1d(np.asarray(costs, dtype=np.float64))
+        if costs.ndim != 1 or costs.size < 1 or not (np.isfinite(costs).all() and (costs > 0).all()):
+            raise ValueError("costs must be a non-empty list of finite numbers > 0")
+        s = self.params.point_weights()
+        if not self._on_device:
+            self.setup_data_on_device()
+        self._apply_class_weight(s)
+        y = np.ascontiguousarray(self.params.labels, dtype=self.dtype)
+        Y = np.ascontiguousarray(np.tile(y, (costs.size, 1)))
+        self._learn_lanes(Y, costs, None, imax)
+        self.costs = costs
+        return self
+
+    def learn_multi(self, labels=None, imax=-1, class_weight=None):
         """One-vs-all training on K >= 2 classes (any integer or float labels; default: the parameter's labels): per
         class exactly learn() on the +-1 labels of that class against the rest, the K solves sharing each pass over
-        the kernel matrix. Sets classes [K], alphas [K][n], biases [K], iters_multi [K], traces."""
+        the kernel matrix. Sets classes [K], alphas [K][n], biases [K], iters_multi [K], traces.
+        class_weight {label: w}: class c's problem weighs its own points (the positives) by w[c], all others by 1.
+        Weights set with set_point_weights apply to every class; those an earlier learn() took from
+        Parameter.class_weight are cleared first."""
         labels = self.params.labels if labels is None else labels
         if labels is None:
             raise ValueError("No labels given for training! Maybe the data is only usable for prediction?")
@@ -422,8 +546,14 @@ class CSVM:
             raise ValueError(f"labels must have {self.num_data_points} entries")
         if classes.size < 2:
             raise ValueError("learn_multi needs at least 2 classes")
+        S = None if class_weight is None else one_vs_all_weights(labels, class_weight, self.dtype)
         if not self._on_device:
             self.setup_data_on_device()
+        self._apply_class_weight(None)  # the binary class_weight of an earlier learn() does not reach the classes
+        if S is not None:
+            self._learn_lanes(Y, None, S, imax)
+            self.classes = classes
+            return self
         K, n = Y.shape
         im = self.num_features if imax < 0 else imax
         alphas = np.zeros((K, n), dtype=self.dtype)

@@ -137,11 +137,12 @@ constexpr int CG_PRE = 2;
 // slabs != null: raw_i = sum_{k < P} slabs[k * m + i], summed as panel_reduce_kernel does — from 0 in
 // panel order, and for P >= 16 (its split form) as four quarter sums of ceil(P / 4) panels combined
 // ((q0 + q1) + q2) + q3 — so Ad is bitwise the reduced pass output the other K·p calls see
-template <typename T>
+// DG = T: the scalar diagonal 1/C; DG = row_diag<T>: (1/C)(1/s_i) with point weights (kernels.hpp)
+template <typename T, typename DG>
 __global__ __launch_bounds__(CG_NT) void cg_fin_dad_kernel(const T *__restrict__ raw, const T *__restrict__ slabs,
                                                          int64_t P, int64_t sstride, const T *__restrict__ q,
                                                          const T *__restrict__ d, const T *__restrict__ psum, int G,
-                                                         T QA_cost, T cost_inv, int raw_only, int64_t m,
+                                                         T QA_cost, DG cost_inv, int raw_only, int64_t m,
                                                          T *__restrict__ Ad, T *__restrict__ pdad,
                                                          cg_scalars<T> *sc) {
     if (sc->converged) return;
@@ -175,7 +176,7 @@ __global__ __launch_bounds__(CG_NT) void cg_fin_dad_kernel(const T *__restrict__
     if (blockIdx.x == 0 && threadIdx.x == 0) sc->sp = sp, sc->sqp = sqp;
     T s1 = 0;
     auto one = [&](int64_t i, T r_, T q_, T d_) {
-        const T v = cg_fin_value(r_, q_, d_, sp, sqp, QA_cost, cost_inv, raw_only);
+        const T v = cg_fin_value(r_, q_, d_, sp, sqp, QA_cost, diag_at(cost_inv, i), raw_only);
         Ad[i] = v;
         s1 = cg_acc(s1, d_, v);
     };
@@ -485,10 +486,14 @@ void launch_cg1_delta(const T *pset, int G, double *trace, int64_t trace_cap, cg
 
 template <typename T>
 void launch_cg_fin_dad(const T *raw, const T *slabs, int64_t P, int64_t sstride, const T *q, const T *d, const T *psum,
-                       int G, T QA_cost, T cost_inv, int raw_only, int64_t m, T *Ad, T *pdad, cg_scalars<T> *sc,
-                       hipStream_t s) {
-    hipLaunchKernelGGL(cg_fin_dad_kernel<T>, dim3(RED_BLOCKS), dim3(CG_NT), 0, s, raw, slabs, P, sstride, q, d, psum, G,
-                       QA_cost, cost_inv, raw_only, m, Ad, pdad, sc);
+                       int G, T QA_cost, T cost_inv, const T *sinv, int raw_only, int64_t m, T *Ad, T *pdad,
+                       cg_scalars<T> *sc, hipStream_t s) {
+    if (sinv == nullptr)
+        hipLaunchKernelGGL((cg_fin_dad_kernel<T, T>), dim3(RED_BLOCKS), dim3(CG_NT), 0, s, raw, slabs, P, sstride, q, d,
+                           psum, G, QA_cost, cost_inv, raw_only, m, Ad, pdad, sc);
+    else
+        hipLaunchKernelGGL((cg_fin_dad_kernel<T, row_diag<T>>), dim3(RED_BLOCKS), dim3(CG_NT), 0, s, raw, slabs, P,
+                           sstride, q, d, psum, G, QA_cost, row_diag<T>{ cost_inv, sinv }, raw_only, m, Ad, pdad, sc);
     MI_LAUNCH_CHECK();
 }
 
@@ -568,7 +573,7 @@ void launch_cg_direction(T *d, const T *r, int64_t m, const cg_scalars<T> *sc, h
                                       const cg_scalars<T> *, hipStream_t);                                        \
     template void launch_cg_direction<T>(T *, const T *, int64_t, const cg_scalars<T> *, hipStream_t);             \
     template void launch_cg_fin_dad<T>(const T *, const T *, int64_t, int64_t, const T *, const T *, const T *,    \
-                                       int, T, T, int, int64_t, T *, T *, cg_scalars<T> *, hipStream_t);           \
+                                       int, T, T, const T *, int, int64_t, T *, T *, cg_scalars<T> *, hipStream_t); \
     template void launch_cg_upd_rr<T>(T *, T *, const T *, const T *, const T *, int, const T *, int, int64_t, T *, \
                                       cg_scalars<T> *, hipStream_t);                                                \
     template void launch_cg_dir_sums<T>(T *, const T *, const T *, const T *, int, int, double *, int64_t, int64_t, \

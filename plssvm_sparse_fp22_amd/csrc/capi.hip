@@ -375,6 +375,25 @@ int plssvm_mi_learn_multi(plssvm_mi_ctx *ctx, const void *Y, int64_t nclass, int
     });
 }
 
+int plssvm_mi_set_point_weights(plssvm_mi_ctx *ctx, const void *s) {
+    if (!ctx) return PLSSVM_MI_ERR_ARG;
+    return ctx->call([&](auto &e) {
+        using T = std::remove_reference_t<decltype(e.gamma)>;
+        e.set_point_weights(static_cast<const T *>(s));
+    });
+}
+
+int plssvm_mi_learn_lanes(plssvm_mi_ctx *ctx, const void *Y, int64_t nlane, int64_t ldy, const double *costs, const void *S,
+                          int64_t lds, int64_t imax, double eps, void *alpha_out, double *bias_out, double *delta_trace,
+                          int64_t *iters) {
+    if (!ctx || !Y || !alpha_out || nlane < 1) return PLSSVM_MI_ERR_ARG;
+    return ctx->call([&](auto &e) {
+        using T = std::remove_reference_t<decltype(e.gamma)>;
+        e.learn_lanes(static_cast<const T *>(Y), nlane, ldy, costs, static_cast<const T *>(S), lds, imax, (T) eps,
+                      static_cast<T *>(alpha_out), bias_out, delta_trace, iters);
+    });
+}
+
 int plssvm_mi_time_kp_multi(plssvm_mi_ctx *ctx, int64_t nrhs, int reps, double *ms_per_kp) {
     if (!ctx || nrhs < 1) return PLSSVM_MI_ERR_ARG;
     return ctx->call([&](auto &e) { e.time_kp_multi(nrhs, reps, ms_per_kp); });

@@ -388,6 +388,8 @@ void engine<T>::setup_dense(const T *X, int64_t n_, int64_t d_) {
 template <typename T>
 void engine<T>::finish_setup() {
     lanes = lane_pool{};  // an earlier setup's lanes go before the tile cache is sized; the first multi call allocates anew
+    sinv_h.clear();       // point weights belong to the data they were set for
+    sinv.reset();
     // work split of the implicit matrix over the group (replaces feature_ranges_, gpu_csvm.cpp:136-139)
     partition_superblocks(nb, sim_world > 0 ? sim_rank : rank, sim_world > 0 ? sim_world : world, t0, t1, t_total,
                           tiles_total, tiles_local);
@@ -528,7 +530,7 @@ void engine<T>::generate_q(T *q_out, double *qa_out) {
         launch_q_dense<T>(kf(), XT.get(), n_pad, d, m, xlast.get(), q.get(), stream);
     }
     ctr_kmm = host_kernel<T>(kernel, degree, gamma, coef0, xlast_h.data(), xlast_h.data(), d);
-    QA_cost = ctr_kmm + T(1) / cost;
+    QA_cost = ctr_kmm + diag_m();
     q_gen_h.resize((size_t) std::max<int64_t>(m, 0));
     if (m > 0) MI_HIP_CHECK(hipMemcpyAsync(q_gen_h.data(), q.get(), sizeof(T) * (size_t) m, hipMemcpyDeviceToHost, stream));
     MI_HIP_CHECK(hipStreamSynchronize(stream));
@@ -551,7 +553,7 @@ void engine<T>::set_q(const T *q_host) {
     // a caller's q equal to the generated one keeps the centered finalize; any other q is used as given
     q_gen = (int64_t) q_gen_h.size() == m && (m == 0 || std::memcmp(q_host, q_gen_h.data(), sizeof(T) * (size_t) m) == 0);
     if (!have_q) {
-        QA_cost = host_kernel<T>(kernel, degree, gamma, coef0, xlast_h.data(), xlast_h.data(), d) + T(1) / cost;
+        QA_cost = host_kernel<T>(kernel, degree, gamma, coef0, xlast_h.data(), xlast_h.data(), d) + diag_m();
         have_q = true;
     }
 }
@@ -573,8 +575,8 @@ void engine<T>::kp_slab_reduce(const cg_lane &L, const cg_scalars<T> *status) {
 template <typename T>
 void engine<T>::kp_fin(const cg_lane &L, const T *p, T *out, T add, bool overwrite, const cg_scalars<T> *status) {
     const int flags = (overwrite ? 1 : 0) | ((sim_world > 0 && sim_rank != 0 && !shard) ? 2 : 0);
-    launch_kp_finalize<T>(L.raw + v0, qf() + v0, p + v0, L.sc, QAf(), cost_inv(), add, flags, vn, out + v0, status,
-                          stream);
+    launch_kp_finalize<T>(L.raw + v0, qf() + v0, p + v0, L.sc, L.QA, L.cost_inv, L.sinv ? L.sinv + v0 : nullptr, add, flags,
+                          vn, out + v0, status, stream);
 }
 
 // out = (overwrite ? 0 : out) + add * Q~ p   — run_device_kernel + device_reduction
@@ -672,8 +674,8 @@ cg_scalars<T> engine<T>::cg_scalars_init(T eps, bool force) {
 template <typename T>
 void engine<T>::cg_fin_dad(const cg_lane &L, const T *v, T *pd, const T *slabs, int64_t P) {
     const int raw_only = (sim_world > 0 && sim_rank != 0 && !shard) ? 1 : 0;
-    launch_cg_fin_dad<T>(L.raw + v0, slabs, P, m, qf() + v0, v + v0, gathered ? cgp_g.get() : L.cgp, G, QAf(), cost_inv(),
-                         raw_only, vn, L.Ad + v0, pd, L.sc, stream);
+    launch_cg_fin_dad<T>(L.raw + v0, slabs, P, m, qf() + v0, v + v0, gathered ? cgp_g.get() : L.cgp, G, L.QA, L.cost_inv,
+                         L.sinv ? L.sinv + v0 : nullptr, raw_only, vn, L.Ad + v0, pd, L.sc, stream);
 }
 
 // alpha = delta / (d . Ad) (:116); x += alpha d; r = b every 50th iteration, else r -= alpha Ad   (:119-132)
@@ -770,7 +772,7 @@ void engine<T>::cg_product(const T *v, T *pd) {
         // one GPU, factored sparse linear: CSC pass, then the row-block CSR pass with the finalize and
         // the v.Ad partials fused (spmv.hpp)
         spmv_pass_csc(v, st);
-        launch_rowblock_fin<T>(csr.rb_csr, w.get(), d, q.get(), v, L.cgp, QA_cost, cost_inv(), L.Ad, pd, st, stream);
+        launch_rowblock_fin<T>(csr.rb_csr, w.get(), d, q.get(), v, L.cgp, L.QA, L.cost_inv, L.sinv, L.Ad, pd, st, stream);
         fin = true;
     } else if (one_gpu_factored && csr.spmv_csr.P > 1) {
         // one GPU, factored sparse linear: the CSR pass's panel slabs are summed by cg_fin_dad
@@ -780,7 +782,7 @@ void engine<T>::cg_product(const T *v, T *pd) {
         P = csr.spmv_csr.P;
     } else {
         // offered to the K·p: a path that forms Ad and the partials in its own last kernel sets kp_fin_done
-        const kp_fin_t f{ qf(), v, gathered ? cgp_g.get() : L.cgp, G, QAf(), cost_inv(), L.Ad, pd };
+        const kp_fin_t f{ qf(), v, gathered ? cgp_g.get() : L.cgp, G, L.QA, L.cost_inv, L.sinv, L.Ad, pd };
         kp_fin_req = (sim_world > 0 && sim_rank != 0 && !shard) ? nullptr : &f;
         kp_fin_done = false;
         ctr_now = ctr_active();
@@ -978,11 +980,11 @@ void engine<T>::solve_cg(const T *b_host, const T *q_host, int64_t imax, T eps, 
 }
 
 template <typename T>
-void engine<T>::learn_tail(const T *y, const T *q_host, T *alpha, double *bias_out) const {
+void engine<T>::learn_tail(const T *y, const T *q_host, T QA, T *alpha, double *bias_out) const {
     T s = 0, qa = 0;
     for (int64_t i = 0; i < m; ++i) s += alpha[i];
     for (int64_t i = 0; i < m; ++i) qa = std::fma(q_host[i], alpha[i], qa);
-    const T bias = y[m] + QA_cost * s - qa;  // (:257)
+    const T bias = y[m] + QA * s - qa;  // (:257); QA = k_mm + (1/C)(1/s_m) with point weights
     alpha[m] = -s;                           // (:258)
     if (bias_out) *bias_out = (double) bias;
 }
@@ -998,7 +1000,7 @@ void engine<T>::learn(const T *y, int64_t imax, T eps, T *alpha_out, double *bia
     for (int64_t i = 0; i < m; ++i) bh[i] = y[i] - y[m];  // b = y[0..m) - y[m]   (:238-239)
     if (imax < 0) imax = d;                                // solver_CG(b, num_features_, ...)  (:256)
     solve_cg(bh.data(), nullptr, imax, eps, alpha_out, trace_out, iters);
-    learn_tail(y, qh.data(), alpha_out, bias_out);
+    learn_tail(y, qh.data(), QA_cost, alpha_out, bias_out);
 }
 
 // time_kp's cache eviction: reads n 16-byte words (their contents are never used; the sink is written only
@@ -1097,15 +1099,15 @@ void engine<T>::need_pool() {
 }
 
 template <typename T>
-int64_t engine<T>::lane_bytes() const {
-    return ((int64_t) LV_COUNT * q.size() + kp_wgs * KP_REC + 8 * RED_BLOCKS) * (int64_t) sizeof(T) +
+int64_t engine<T>::lane_bytes(bool with_sinv) const {
+    return ((int64_t) (LV_COUNT + (with_sinv ? 1 : 0)) * q.size() + kp_wgs * KP_REC + 8 * RED_BLOCKS) * (int64_t) sizeof(T) +
            (int64_t) sizeof(cg_scalars<T>);
 }
 
 // Lanes are taken from what the setup (tile cache included) left free, keeping 256 MiB for the single path's own
 // later needs (traces, a captured block): the widest of W, W / 2, ... that fits; 1 = not even two lanes fit.
 template <typename T>
-int engine<T>::multi_width_next() const {
+int engine<T>::multi_width_next(bool with_sinv) const {
     if (!multi_batched()) return 1;
     if (lanes.width > 0) return lanes.width;
     size_t free_b = 0, total_b = 0;
@@ -1113,15 +1115,15 @@ int engine<T>::multi_width_next() const {
     MI_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
     const int64_t room = (int64_t) free_b - ((int64_t) 256 << 20);
     int w = multi_opt >= 2 ? std::min(multi_opt, KP_MULTI_W) : KP_MULTI_W;
-    while (w >= 2 && (int64_t) w * lane_bytes() > room) w /= 2;
+    while (w >= 2 && (int64_t) w * lane_bytes(with_sinv) > room) w /= 2;
     return std::max(w, 1);
 }
 
 template <typename T>
-int engine<T>::multi_lanes() {
+int engine<T>::multi_lanes(bool with_sinv) {
     if (!multi_batched()) return 1;
     if (lanes.width > 0) return lanes.width;
-    for (int w = multi_width_next(); w >= 2; w /= 2) {
+    for (int w = multi_width_next(with_sinv); w >= 2; w /= 2) {
         try {
             lanes.vstride = q.size();
             lanes.sstride = kp_wgs * KP_REC;
@@ -1129,7 +1131,9 @@ int engine<T>::multi_lanes() {
             lanes.slab.alloc((int64_t) w * lanes.sstride, stream, false);
             lanes.part.alloc((int64_t) w * 8 * RED_BLOCKS, stream);
             lanes.sc.alloc(w, stream);
+            if (with_sinv) lanes.sinv.alloc((int64_t) w * lanes.vstride, stream);
             lanes.width = w;
+            lanes_own_diag();
             return w;
         } catch (const mi_error &e) {
             if (e.code != -4) throw;
@@ -1139,6 +1143,28 @@ int engine<T>::multi_lanes() {
     }
     lanes.width = 1;
     return 1;
+}
+
+// The weight vectors of a pool that was allocated without them (an earlier call had no per-lane weights). No room: the
+// caller runs its lanes one after another.
+template <typename T>
+bool engine<T>::need_lane_sinv() {
+    if (lanes.width < 2) return false;
+    if (lanes.sinv.size() >= (int64_t) lanes.width * lanes.vstride) return true;
+    try {
+        lanes.sinv.alloc((int64_t) lanes.width * lanes.vstride, stream);
+    } catch (const mi_error &e) {
+        if (e.code != -4) throw;
+        (void) hipGetLastError();
+        lanes.sinv.reset();
+        return false;
+    }
+    return true;
+}
+
+template <typename T>
+void engine<T>::lanes_own_diag() {
+    lanes.diag.assign((size_t) std::max(lanes.width, 0), lane_diag{ cost_inv(), QAf(), sinv_dev() });
 }
 
 // One pass over the tiles for the vectors `kind` of lanes [c0, c0 + nvec); flags: the lanes' stop flags apply.
@@ -1207,7 +1233,9 @@ void engine<T>::solve_cg_group(const T *B, int nvec, int64_t ld, int64_t imax, T
     kp_raw(lane_v(LV_X, 0), nullptr);
     for (int c = 0; c < nvec; ++c) {
         const cg_lane L = pool_lane(c);
-        kp_fin(own_lane(), L.x, L.r, T(-1), false, nullptr);
+        cg_lane S = own_lane();  // the shared raw and sums, the lane's diagonal
+        S.cost_inv = L.cost_inv, S.QA = L.QA, S.sinv = L.sinv;
+        kp_fin(S, L.x, L.r, T(-1), false, nullptr);
         cg_delta0(L);
         cg_dir(L, 1);
     }
@@ -1256,6 +1284,7 @@ void engine<T>::solve_cg_multi(const T *B, int64_t nrhs, int64_t ld, const T *q_
         return;
     }
     cg_active = false;  // the group borrows sc, red, raw and the slab of the single solve
+    lanes_own_diag();
     for (int64_t c0 = 0; c0 < nrhs; c0 += W)
         solve_cg_group(B + c0 * ld, (int) std::min<int64_t>(W, nrhs - c0), ld, imax, eps, X_out + c0 * ld,
                        trace_out ? trace_out + c0 * (imax + 1) : nullptr, iters ? iters + c0 : nullptr);
@@ -1276,6 +1305,7 @@ void engine<T>::kp_multi(const T *q_host, const T *P, T *RET, int64_t nrhs, int6
     set_q(q_host);
     need_pool();
     cg_active = false;
+    lanes_own_diag();
     for (int64_t c0 = 0; c0 < nrhs; c0 += W) {
         const int nvec = (int) std::min<int64_t>(W, nrhs - c0);
         MI_HIP_CHECK(hipMemsetAsync(lanes.sc.get(), 0, sizeof(cg_scalars<T>) * (size_t) nvec, stream));
@@ -1300,18 +1330,149 @@ void engine<T>::kp_multi(const T *q_host, const T *P, T *RET, int64_t nrhs, int6
 template <typename T>
 void engine<T>::learn_multi(const T *Y, int64_t nclass, int64_t ldy, int64_t imax, T eps, T *alpha_out, double *bias_out,
                             double *trace_out, int64_t *iters) {
+    learn_lanes(Y, nclass, ldy, nullptr, nullptr, 0, imax, eps, alpha_out, bias_out, trace_out, iters);
+}
+
+// ---- point weights and lanes that differ in their diagonal ---------------------------------------
+template <typename T>
+void engine<T>::check_weights(const T *s, int64_t count) {
+    for (int64_t i = 0; i < count; ++i) {
+        const T r = T(1) / s[i];
+        if (!(s[i] > T(0)) || !std::isfinite(s[i]) || !(r > T(0)) || !std::isfinite(r))
+            throw mi_error(-1, "point weight " + std::to_string(i) + " is not a finite number > 0 (with a finite reciprocal)");
+    }
+}
+
+template <typename T>
+void engine<T>::set_sinv(const std::vector<T> &sinv_new) {
+    MI_HIP_CHECK(hipSetDevice(device));
+    if (!sinv_new.empty()) {
+        if (sinv.size() < q.size()) sinv.alloc(q.size(), stream);
+        if (m > 0) MI_HIP_CHECK(hipMemcpyAsync(sinv.get(), sinv_new.data(), sizeof(T) * (size_t) m, hipMemcpyHostToDevice, stream));
+        MI_HIP_CHECK(hipStreamSynchronize(stream));
+    }
+    if (&sinv_new != &sinv_h) sinv_h = sinv_new;
+    // a q in place keeps a QA_cost that matches the diagonal, as generate_q would form it now
+    if (have_q) QA_cost = host_kernel<T>(kernel, degree, gamma, coef0, xlast_h.data(), xlast_h.data(), d) + diag_m();
+    graph_reset();  // a captured CG block holds the pointer and QA_cost
+}
+
+template <typename T>
+void engine<T>::set_point_weights(const T *s) {
+    if (!have_data) throw mi_error(-1, "point weights are set after a setup (they belong to its points)");
+    std::vector<T> inv;
+    if (s != nullptr) {
+        check_weights(s, n);
+        inv.resize((size_t) n);
+        for (int64_t i = 0; i < n; ++i) inv[(size_t) i] = T(1) / s[i];
+    }
+    set_sinv(inv);
+}
+
+template <typename T>
+void engine<T>::learn_lanes(const T *Y, int64_t nlane, int64_t ldy, const double *costs, const T *S, int64_t lds,
+                            int64_t imax, T eps, T *alpha_out, double *bias_out, double *trace_out, int64_t *iters) {
     need_data();
     if (Y == nullptr) throw mi_error(-1, "No labels given for training! Maybe the data is only usable for prediction?");
-    if (nclass < 1) throw mi_error(-1, "at least one class is needed");
+    if (nlane < 1) throw mi_error(-1, "at least one class is needed");
     if (ldy < n) throw mi_error(-1, "the leading dimension is smaller than the number of points");
-    std::vector<T> qh(std::max<int64_t>(m, 1)), bh((size_t) (nclass * ldy));  // b rows ldy apart, like alpha_out's
-    generate_q(qh.data(), nullptr);
-    for (int64_t c = 0; c < nclass; ++c)
-        for (int64_t i = 0; i < m; ++i) bh[(size_t) (c * ldy + i)] = Y[c * ldy + i] - Y[c * ldy + m];  // b = y - y_m
-    if (imax < 0) imax = d;
-    solve_cg_multi(bh.data(), nclass, ldy, nullptr, imax, eps, alpha_out, trace_out, iters);
-    for (int64_t c = 0; c < nclass; ++c)
-        learn_tail(Y + c * ldy, qh.data(), alpha_out + c * ldy, bias_out ? bias_out + c : nullptr);
+    if (S != nullptr && lds != 0 && lds < n) throw mi_error(-1, "the weights' leading dimension is smaller than the number of points");
+    std::vector<T> cost_k((size_t) nlane, cost);
+    if (costs != nullptr)
+        for (int64_t k = 0; k < nlane; ++k) {
+            const T c = (T) costs[k], r = T(1) / c;
+            if (!(costs[k] > 0) || !std::isfinite(c) || !(c > T(0)) || !std::isfinite(r) || !(r > T(0)))
+                throw mi_error(-1, "cost " + std::to_string(k) + " is not a finite number > 0");
+            cost_k[(size_t) k] = c;
+        }
+    const bool per_lane = S != nullptr && lds != 0;
+    if (S != nullptr)
+        for (int64_t k = 0; k < (per_lane ? nlane : 1); ++k) check_weights(S + k * lds, n);
+    auto recip = [&](const T *s) {
+        std::vector<T> inv((size_t) n);
+        for (int64_t i = 0; i < n; ++i) inv[(size_t) i] = T(1) / s[i];
+        return inv;
+    };
+    MI_HIP_CHECK(hipSetDevice(device));
+    const T cost0 = cost;
+    const std::vector<T> sinv0 = sinv_h;
+    bool cost_touched = false, sinv_touched = false;  // what the call changed on the engine, for restore
+    auto run = [&]() {
+        if (S != nullptr && !per_lane) {  // one row for all lanes: the context's weights for this call
+            sinv_touched = true;
+            set_sinv(recip(S));
+        }
+        std::vector<T> qh(std::max<int64_t>(m, 1)), bh((size_t) (nlane * ldy));  // b rows ldy apart, like alpha_out's
+        generate_q(qh.data(), nullptr);
+        for (int64_t c = 0; c < nlane; ++c)
+            for (int64_t i = 0; i < m; ++i) bh[(size_t) (c * ldy + i)] = Y[c * ldy + i] - Y[c * ldy + m];  // b = y - y_m
+        if (imax < 0) imax = d;
+        const int64_t cap = imax + 1;
+        const int W = nlane == 1 ? 1 : multi_lanes(per_lane);
+        if (W < 2 || (per_lane && !need_lane_sinv())) {
+            // one after another through the single solve, the engine's cost and weights set per lane
+            for (int64_t k = 0; k < nlane; ++k) {
+                cost_touched = cost_touched || costs != nullptr;
+                cost = cost_k[(size_t) k];
+                if (per_lane) {
+                    sinv_touched = true;
+                    set_sinv(recip(S + k * lds));
+                }
+                QA_cost = ctr_kmm + diag_m();  // generate_q's, at this lane's cost and weights
+                solve_cg(bh.data() + k * ldy, nullptr, imax, eps, alpha_out + k * ldy, trace_out ? trace_out + k * cap : nullptr,
+                         iters ? iters + k : nullptr);
+                learn_tail(Y + k * ldy, qh.data(), QA_cost, alpha_out + k * ldy, bias_out ? bias_out + k : nullptr);
+            }
+            return;
+        }
+        need_pool();
+        cg_active = false;  // the group borrows sc, red, raw and the slab of the single solve
+        std::vector<T> QA((size_t) nlane);
+        for (int64_t c0 = 0; c0 < nlane; c0 += W) {
+            const int nvec = (int) std::min<int64_t>(W, nlane - c0);
+            std::vector<std::vector<T>> inv((size_t) nvec);  // alive until the group's last synchronisation
+            for (int c = 0; c < nvec; ++c) {
+                const int64_t k = c0 + c;
+                const T cinv = T(1) / cost_k[(size_t) k];
+                T dm = cinv;
+                const T *sv = sinv_dev();
+                if (per_lane) {
+                    inv[(size_t) c] = recip(S + k * lds);
+                    MI_HIP_CHECK(hipMemcpyAsync(lane_sinv(c), inv[(size_t) c].data(), sizeof(T) * (size_t) m, hipMemcpyHostToDevice, stream));
+                    sv = lane_sinv(c);
+                    dm = cinv * inv[(size_t) c][(size_t) m];
+                } else if (weighted()) {
+                    dm = cinv * sinv_h[(size_t) m];
+                }
+                QA[(size_t) k] = ctr_kmm + dm;
+                lanes.diag[(size_t) c] = lane_diag{ cinv, QA[(size_t) k], sv };
+            }
+            solve_cg_group(bh.data() + c0 * ldy, nvec, ldy, imax, eps, alpha_out + c0 * ldy,
+                           trace_out ? trace_out + c0 * cap : nullptr, iters ? iters + c0 : nullptr);
+        }
+        for (int64_t k = 0; k < nlane; ++k)
+            learn_tail(Y + k * ldy, qh.data(), QA[(size_t) k], alpha_out + k * ldy, bias_out ? bias_out + k : nullptr);
+    };
+    // only what was touched: an unweighted learn_multi keeps its captured graph and pays no extra synchronisation
+    auto restore = [&]() {
+        cost = cost0;
+        if (sinv_touched) {
+            set_sinv(sinv0);  // with the QA_cost that goes with them
+        } else if (cost_touched) {
+            QA_cost = ctr_kmm + diag_m();  // generate_q's (it ran before the cost moved)
+            graph_reset();
+        }
+    };
+    try {
+        run();
+    } catch (...) {
+        try {
+            restore();
+        } catch (...) {
+        }
+        throw;
+    }
+    restore();
 }
 
 // time_kp's K·p time for the batched product of nrhs resident vectors (groups of at most the width; one at a time
@@ -1324,7 +1485,7 @@ void engine<T>::time_kp_multi(int64_t nrhs, int reps, double *ms_kp) {
     MI_HIP_CHECK(hipSetDevice(device));
     if (reps < 1) reps = 1;
     const int W = multi_lanes();
-    if (W >= 2) need_pool();
+    if (W >= 2) need_pool(), lanes_own_diag();
     cg_active = false;
     std::vector<T> ph(std::max<int64_t>(m, 1));
     for (int64_t i = 0; i < m; ++i) ph[i] = T(1) + T((i * 2654435761ull) % 1000) / T(1000);
@@ -1361,7 +1522,7 @@ void engine<T>::time_kp_multi(int64_t nrhs, int reps, double *ms_kp) {
 template <typename T>
 int64_t engine<T>::device_bytes() const {
     return XT.bytes() + norms.bytes() + xlast.bytes() + partial.bytes() + kc.bytes() + q.bytes() * 10 + w.bytes() +
-           csr_bytes() + lanes.bytes();
+           csr_bytes() + lanes.bytes() + sinv.bytes();
 }
 
 template struct engine<float>;

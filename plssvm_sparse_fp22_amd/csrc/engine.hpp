@@ -189,6 +189,7 @@ struct engine : engine_base {
         const T *q, *d, *psum;
         int G;
         T QA_cost, cost_inv;
+        const T *sinv;  // point weights: 1/s_i beside q (whole length), else null
         T *Ad, *pdad;
     };
     const kp_fin_t *kp_fin_req = nullptr;
@@ -221,6 +222,18 @@ struct engine : engine_base {
 
     kfun<T> kf() const { return kfun<T>{ kernel, degree, gamma, coef0 }; }
     T cost_inv() const { return T(1) / cost; }
+    // ---- point weights (plssvm_mi_set_point_weights): cost C s_i for point i ----
+    // Only the diagonal of Q~ changes: row i's 1/C becomes (1/C)(1/s_i), QA_cost = k_mm + (1/C)(1/s_m); both
+    // reciprocals and their product are rounded in T, so s = 1 gives 1/C exactly. sinv_h: the n reciprocals (empty =
+    // no weights), sinv: the first m of them on the device, zero padded like q. Any setup clears them.
+    std::vector<T> sinv_h;
+    dev_buf<T> sinv;
+    bool weighted() const { return !sinv_h.empty(); }
+    const T *sinv_dev() const { return weighted() ? sinv.get() : nullptr; }
+    T diag_m() const { return weighted() ? cost_inv() * sinv_h[(size_t) m] : cost_inv(); }  // the last point's diagonal
+    static void check_weights(const T *s, int64_t count);  // finite and > 0, else ERR_ARG
+    void set_sinv(const std::vector<T> &sinv_new);          // the reciprocals (n, or empty: none); QA_cost follows
+    void set_point_weights(const T *s);                    // s[n], null clears
     bool factored() const;
     void need_data() const;
     void need_dense_kernel_data() const;  // the sparse setups' first check: throws on a kernel that takes dense data only
@@ -245,6 +258,10 @@ struct engine : engine_base {
     // A non-owning view: the engine's own vectors (own_lane: the single solve) or lane c of the pool below
     // (pool_lane). The single solve and a batched group are the same step functions on different views.
     struct cg_lane {
+        // the lane's diagonal: 1/C, the QA_cost that goes with it (the centred one where ctr_active()), and the rows'
+        // 1/s_i (null: no point weights) — what kp_fin, cg_fin_dad and cg_product hand to the finalize kernels
+        T cost_inv, QA;
+        const T *sinv;
         T *x, *r, *d, *Ad, *b, *raw;
         T *cgp;   // 6 RED_BLOCKS: sum d / sum q d, then d.Ad, then r.r
         T *red;   // 2 RED_BLOCKS: the K·p sums and delta0
@@ -256,12 +273,14 @@ struct engine : engine_base {
         T *prr() const { return cgp + 4 * RED_BLOCKS; }
     };
     cg_lane own_lane() const {
-        return { x.get(), r.get(), dv.get(), Ad.get(), b.get(), raw.get(), cgp.get(), red.get(), partial.get(), sc.get(),
-                 trace.get(), trace_cap };
+        return { cost_inv(), QAf(), sinv_dev(), x.get(), r.get(), dv.get(), Ad.get(), b.get(), raw.get(), cgp.get(),
+                 red.get(), partial.get(), sc.get(), trace.get(), trace_cap };
     }
     cg_lane pool_lane(int c) const {
-        return { lane_v(LV_X, c), lane_v(LV_R, c), lane_v(LV_D, c), lane_v(LV_AD, c), lane_v(LV_B, c), lane_v(LV_RAW, c),
-                 lane_cgp(c), lane_red(c), lanes.slab.get() + (int64_t) c * lanes.sstride, lanes.sc.get() + c,
+        const lane_diag &dg = lanes.diag[(size_t) c];
+        return { dg.cost_inv, dg.QA, dg.sinv, lane_v(LV_X, c), lane_v(LV_R, c), lane_v(LV_D, c), lane_v(LV_AD, c),
+                 lane_v(LV_B, c), lane_v(LV_RAW, c), lane_cgp(c), lane_red(c),
+                 lanes.slab.get() + (int64_t) c * lanes.sstride, lanes.sc.get() + c,
                  lanes.trace.get() + (int64_t) c * lanes.trace_cap, lanes.trace_cap };
     }
     // The steps take the rows [v0, v0 + vn), sum the G ranks' partials (gather_partials) and use qf() / QAf() /
@@ -286,7 +305,7 @@ struct engine : engine_base {
     // iterations until the next host poll: 4, 8, 16, ... up to the first reset, then blocks of CG_RESET
     static int64_t poll_batch(int64_t done, int64_t imax, int64_t &batch);
     // csvm::learn's end (csvm.cpp:257-258): alpha[m] = -sum alpha, bias = y_m + QA_cost sum alpha - q . alpha
-    void learn_tail(const T *y, const T *q_host, T *alpha, double *bias_out) const;
+    void learn_tail(const T *y, const T *q_host, T QA, T *alpha, double *bias_out) const;
 
     void cg_begin(const T *b_host, const T *q_host, T eps, bool force, double *delta0_out, int64_t trace_len);
     void cg_iter(int reset);
@@ -311,7 +330,16 @@ struct engine : engine_base {
     // raw and partial (the shared first product Q~ x0, x0 = 1).
     // Batched: the pairwise tile path on one rank (multi_batched); everywhere else, and when not even two lanes fit
     // in device memory, the same entry points run the right-hand sides one after another through solve_cg / kp_host.
+    struct lane_diag {
+        T cost_inv, QA;
+        const T *sinv;
+    };
     struct lane_pool {
+        // every lane's diagonal (cg_lane), set by the batched entry points before they run a group: the engine's own
+        // (lanes_own_diag: the one-vs-all classes) or the lane's cost and weights (learn_lanes)
+        std::vector<lane_diag> diag;
+        dev_buf<T> sinv;                   // [width][vstride] per-lane 1/s_i: allocated by the first call that passes
+                                           // per-lane weights (need_lane_sinv), never for lanes that differ in C only
         int width = 0;                     // lanes allocated: 0 = not yet, 1 = none fit (one at a time)
         int64_t vstride = 0, sstride = 0;  // elements between two lanes' vectors / slabs
         dev_buf<T> vec;                    // [LV_COUNT][width][vstride], zero padded like the engine's vectors
@@ -320,7 +348,9 @@ struct engine : engine_base {
         dev_buf<cg_scalars<T>> sc;         // [width]
         dev_buf<double> trace;             // [width][trace_cap]
         int64_t trace_cap = 0;
-        int64_t bytes() const { return vec.bytes() + slab.bytes() + part.bytes() + sc.bytes() + trace.bytes(); }
+        int64_t bytes() const {
+            return vec.bytes() + slab.bytes() + part.bytes() + sc.bytes() + trace.bytes() + sinv.bytes();
+        }
     };
     enum lane_vec { LV_X = 0, LV_R, LV_D, LV_AD, LV_B, LV_RAW, LV_COUNT };
     lane_pool lanes;
@@ -329,9 +359,13 @@ struct engine : engine_base {
     T *lane_cgp(int c) const { return lanes.part.get() + (int64_t) c * 8 * RED_BLOCKS; }
     T *lane_red(int c) const { return lane_cgp(c) + 6 * RED_BLOCKS; }
     bool multi_batched() const;           // this setup runs the batched path (given memory for two lanes)
-    int64_t lane_bytes() const;           // device memory of one lane
-    int multi_width_next() const;         // the width the next multi call would use (1: one at a time); allocates nothing
-    int multi_lanes();                    // the lanes, allocated at the first call (width halved until it fits)
+    int64_t lane_bytes(bool with_sinv = false) const;  // device memory of one lane (with_sinv: and its weight vector)
+    // the width the next multi call would use (1: one at a time); allocates nothing
+    int multi_width_next(bool with_sinv = false) const;
+    int multi_lanes(bool with_sinv = false);  // the lanes, allocated at the first call (width halved until it fits)
+    bool need_lane_sinv();                // the per-lane weight vectors of an allocated pool; false: no room for them
+    T *lane_sinv(int c) const { return lanes.sinv.get() + (int64_t) c * lanes.vstride; }
+    void lanes_own_diag();                // every lane: the engine's own cost, QA_cost and weights
     void need_pool();                     // the steps' group / shard / centring handling is the identity here
     void tiles_multi(int kind, int c0, int nvec, bool flags);  // one pass over the tiles for lanes [c0, c0 + nvec)
     // vectors `kout` of lanes [c0, c0 + nvec) = (overwrite ? 0 : kout) + add * Q~ (vectors `kin`): kp_sums per lane, one
@@ -345,6 +379,11 @@ struct engine : engine_base {
     void kp_multi(const T *q_host, const T *P, T *RET, int64_t nrhs, int64_t ld, T add);
     void learn_multi(const T *Y, int64_t nclass, int64_t ldy, int64_t imax, T eps, T *alpha_out, double *bias_out,
                      double *trace_out, int64_t *iters);
+    // lane k = learn on labels Y[k] with cost costs[k] (null: the engine's) and point weights S[k] (null: the engine's;
+    // lds == 0: S is one row for all lanes): batched where multi_batched(), else one after another with the engine's
+    // cost and weights set per lane; both are as before on return (also when it throws)
+    void learn_lanes(const T *Y, int64_t nlane, int64_t ldy, const double *costs, const T *S, int64_t lds, int64_t imax,
+                     T eps, T *alpha_out, double *bias_out, double *trace_out, int64_t *iters);
     void time_kp_multi(int64_t nrhs, int reps, double *ms_kp);
 
     // sparse paths (sparse.hip)

@@ -590,12 +590,14 @@ __global__ __launch_bounds__(256) void exp_combine_kernel(const T *__restrict__ 
 // the combine of a CG iteration's K·p fused with the iteration's finalize (cg_fin_dad_kernel): rows [r0, r1) =
 // the CG's own rows, in cg_fin_dad_kernel's grid (RED_BLOCKS x CG_NT), element order and partials — Ad and the
 // d.Ad partials bit for bit those of the two launches, raw is not written
-template <typename T>
+// DG = T: the scalar diagonal 1/C; DG = row_diag<T>: (1/C)(1/s_i) with point weights (kernels.hpp; sinv is whole-length
+// like q here)
+template <typename T, typename DG>
 __global__ __launch_bounds__(cgk::CG_NT) void exp_combine_fin_kernel(
     const T *__restrict__ e, const T *__restrict__ cb, const T *__restrict__ w, const T *__restrict__ hdiag, const T *__restrict__ hs,
     const T *__restrict__ hslab, int G, const T *__restrict__ jslab, int P, const T *__restrict__ raw,
     const T *__restrict__ ssc, T kappa, int64_t r0, int64_t r1, const T *__restrict__ q, const T *__restrict__ d,
-    const T *__restrict__ psum, int GP, T QA_cost, T cost_inv, T *__restrict__ Ad, T *__restrict__ pdad,
+    const T *__restrict__ psum, int GP, T QA_cost, DG cost_inv, T *__restrict__ Ad, T *__restrict__ pdad,
     cg_scalars<T> *sc) {
     if (sc->converged) return;
     __shared__ T red[cgk::CG_NT / 64], bc[1];
@@ -608,7 +610,7 @@ __global__ __launch_bounds__(cgk::CG_NT) void exp_combine_fin_kernel(
         const int64_t i = r0 + k;
         const T rw = exp_combine_row<T>(e, cb, w, hdiag, nullptr, hs, hslab, G, jslab, P, raw, ssc, kappa, i, r0, r1, 0);
         const T di = d[i];
-        const T v = cgk::cg_fin_value(rw, q[i], di, sp, sqp, QA_cost, cost_inv, 0);
+        const T v = cgk::cg_fin_value(rw, q[i], di, sp, sqp, QA_cost, diag_at(cost_inv, i), 0);
         Ad[i] = v;
         s1 = cgk::cg_acc(s1, di, v);
     }
@@ -858,11 +860,15 @@ void engine<T>::expansion_kp_raw(const T *p, const cg_scalars<T> *status, bool w
         (shard || (world == 1 && sim_world == 0))) {
         flush_psum();
         const kp_fin_t &f = *kp_fin_req;
-        hipLaunchKernelGGL(exp_combine_fin_kernel<T>, dim3(RED_BLOCKS), dim3(cgk::CG_NT), 0, stream,
-                           kernel == 2 ? csr.e.get() : nullptr, cb, w, ex.hdiag.get(), ex.hs.get(),
-                           ex.G > 1 ? ex.hslab.get() : nullptr, ex.G, jfuse ? pc.partial.get() : nullptr, (int) pc.P,
-                           raw.get(), csr.ssc.get(), kappa, r0, r1, f.q, f.d, f.psum, f.G, f.QA_cost, f.cost_inv, f.Ad,
-                           f.pdad, sc.get());
+        auto fin = [&](auto kern, auto dg) {
+            hipLaunchKernelGGL(kern, dim3(RED_BLOCKS), dim3(cgk::CG_NT), 0, stream,
+                               kernel == 2 ? csr.e.get() : nullptr, cb, w, ex.hdiag.get(), ex.hs.get(),
+                               ex.G > 1 ? ex.hslab.get() : nullptr, ex.G, jfuse ? pc.partial.get() : nullptr, (int) pc.P,
+                               raw.get(), csr.ssc.get(), kappa, r0, r1, f.q, f.d, f.psum, f.G, f.QA_cost, dg, f.Ad,
+                               f.pdad, sc.get());
+        };
+        if (f.sinv == nullptr) fin(exp_combine_fin_kernel<T, T>, f.cost_inv);
+        else fin(exp_combine_fin_kernel<T, row_diag<T>>, row_diag<T>{ f.cost_inv, f.sinv });
         MI_LAUNCH_CHECK();
         kp_fin_done = true;
         return;  // sharded (or one rank): nothing to gather
@@ -926,7 +932,7 @@ template <typename T>
 T engine<T>::QAf() const {
     if (!ctr_active()) return QA_cost;
     // a caller's QA_cost (plssvm_mi_set_qa_cost) that differs from k_mm + 1/C keeps its difference
-    return (T) (ctr_hm + (double) cost_inv()) + (QA_cost - (ctr_kmm + T(1) / cost));
+    return (T) (ctr_hm + (double) diag_m()) + (QA_cost - (ctr_kmm + diag_m()));
 }
 
 template <typename T>

@@ -30,6 +30,24 @@ struct cg_scalars {
     int64_t iters;
 };
 
+// The diagonal of Q~ as the finalize kernels take it: the scalar 1/C, or — with point weights s —
+// 1/C beside the rows' 1/s_i. Each finalize kernel is a template on this type: the scalar instance is the kernel as it
+// always was (same arguments, same code), the row_diag instance reads sinv[i] beside q[i]. (1/C)(1/s_i) is rounded in
+// T before it meets p_i; s_i = 1 gives 1/C exactly.
+template <typename T>
+struct row_diag {
+    T cost_inv;
+    const T *sinv;  // the kernel's own row range (offset like q)
+};
+template <typename T>
+__host__ __device__ __forceinline__ T diag_at(T cost_inv, int64_t) {
+    return cost_inv;
+}
+template <typename T>
+__host__ __device__ __forceinline__ T diag_at(const row_diag<T> &dg, int64_t i) {
+    return dg.cost_inv * dg.sinv[i];
+}
+
 // ---- dense pairwise tiles -----------------------------------------------------------------------
 // tile edge of the implicit Q~ tiles (rows and columns); n_pad is a multiple of this.
 constexpr int KP_TILE = 128;
@@ -145,9 +163,11 @@ void launch_kp_reduce(const T *partial, int64_t nb, int64_t m, int64_t s0, int64
 
 // ret[i] = (overwrite ? 0 : ret[i]) + add * (raw[i] + (QA - q_i) * sum(p) - sum(q p) + p_i / C)
 // raw may alias ret only when overwrite is false and ... (never aliased by callers).
+// sinv non-null (point weights): the row_diag instance, p_i / C becomes ((1/C) sinv_i) p_i
 template <typename T>
-void launch_kp_finalize(const T *raw, const T *q, const T *p, const cg_scalars<T> *sc, T QA_cost, T cost_inv, T add,
-                        int overwrite, int64_t m, T *ret, const cg_scalars<T> *status, hipStream_t s);
+void launch_kp_finalize(const T *raw, const T *q, const T *p, const cg_scalars<T> *sc, T QA_cost, T cost_inv,
+                        const T *sinv, T add, int overwrite, int64_t m, T *ret, const cg_scalars<T> *status,
+                        hipStream_t s);
 
 // ---- linear factored path: Q~p = X_m (X_m^T p) + rank-1 terms --------------------------------------
 template <typename T>
@@ -190,8 +210,8 @@ void launch_cg_direction(T *d, const T *r, int64_t m, const cg_scalars<T> *sc, h
 // d.Ad partials -> pdad. slabs != null: raw = the P panel slabs [P][sstride] of an unreduced SpMV pass.
 template <typename T>
 void launch_cg_fin_dad(const T *raw, const T *slabs, int64_t P, int64_t sstride, const T *q, const T *d, const T *psum,
-                       int G, T QA_cost, T cost_inv, int raw_only, int64_t m, T *Ad, T *pdad, cg_scalars<T> *sc,
-                       hipStream_t s);
+                       int G, T QA_cost, T cost_inv, const T *sinv, int raw_only, int64_t m, T *Ad, T *pdad,
+                       cg_scalars<T> *sc, hipStream_t s);  // sinv non-null: the row_diag instance
 // alpha = delta / d.Ad (pdad); x += alpha d; r -= alpha Ad and r.r partials -> prr (reset: r = b)
 template <typename T>
 void launch_cg_upd_rr(T *x, T *r, const T *d, const T *Ad, const T *b, int reset, const T *pdad, int G, int64_t m,

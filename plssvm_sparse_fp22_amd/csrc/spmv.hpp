@@ -543,12 +543,13 @@ struct rb_plan {
     }
 };
 
-template <typename T, bool F22>
+// DG = T: the scalar diagonal 1/C; DG = row_diag<T>: (1/C)(1/s_i) with point weights (kernels.hpp)
+template <typename T, bool F22, typename DG>
 __global__ __launch_bounds__(SELL_NT) void sell_rowblock_fin_kernel(
     const sell_chunk *__restrict__ chunks, const int32_t *__restrict__ perm, const uint16_t *__restrict__ idx,
     vals_t<T> val, const int32_t *__restrict__ bpc, int64_t P, int64_t W, int64_t RBK, const T *__restrict__ x,
     int64_t xn, int64_t nrows, const T *__restrict__ q, const T *__restrict__ d, const T *__restrict__ psum,
-    T QA_cost, T cost_inv, T *__restrict__ Ad, T *__restrict__ pdad, const cg_scalars<T> *__restrict__ status) {
+    T QA_cost, DG cost_inv, T *__restrict__ Ad, T *__restrict__ pdad, const cg_scalars<T> *__restrict__ status) {
     constexpr int XW = rb_width<T>(), RB = rb_rows<T>();
     constexpr int SU = sell_unroll<F22>();
     constexpr int RPT = (RB + SELL_NT - 1) / SELL_NT;  // rows per thread
@@ -644,11 +645,11 @@ __global__ __launch_bounds__(SELL_NT) void sell_rowblock_fin_kernel(
         const int t = tid + u * SELL_NT;
         if (t >= rows) break;
         const int64_t i = row0 + t;
-        const T rw = racc[t], qi = q[i], di = d[i];
+        const T rw = racc[t], qi = q[i], di = d[i], dg = diag_at(cost_inv, i);
         T v;
         {
 #pragma clang fp contract(fast)  // cg_fin_dad_kernel's expression
-            v = rw + (QA_cost - qi) * sp - sqp + cost_inv * di;
+            v = rw + (QA_cost - qi) * sp - sqp + dg * di;
             v = T(0) + T(1) * v;
         }
         Ad[i] = v;
@@ -671,13 +672,21 @@ __global__ __launch_bounds__(SELL_NT) void sell_rowblock_fin_kernel(
 
 template <typename T>
 inline void launch_rowblock_fin(const rb_plan<T> &pl, const T *w, int64_t xn, const T *q, const T *d, const T *psum,
-                                T QA_cost, T cost_inv, T *Ad, T *pdad, const cg_scalars<T> *status,
+                                T QA_cost, T cost_inv, const T *sinv, T *Ad, T *pdad, const cg_scalars<T> *status,
                                 hipStream_t stream) {
     if (pl.nblk <= 0) return;
-    auto k = pl.val22.get() ? sell_rowblock_fin_kernel<T, true> : sell_rowblock_fin_kernel<T, false>;
-    hipLaunchKernelGGL(k, dim3((unsigned) pl.nblk), dim3(SELL_NT), 0, stream, pl.chunks.get(), pl.perm.get(),
-                       pl.idx16.get(), pl.vals(), pl.bpc.get(), pl.P, pl.W, pl.RBK, w, xn, pl.nrows, q, d, psum,
-                       QA_cost, cost_inv, Ad, pdad, status);
+    auto launch = [&](auto k, auto dg) {
+        hipLaunchKernelGGL(k, dim3((unsigned) pl.nblk), dim3(SELL_NT), 0, stream, pl.chunks.get(), pl.perm.get(),
+                           pl.idx16.get(), pl.vals(), pl.bpc.get(), pl.P, pl.W, pl.RBK, w, xn, pl.nrows, q, d, psum,
+                           QA_cost, dg, Ad, pdad, status);
+    };
+    if (sinv == nullptr) {
+        launch(pl.val22.get() ? sell_rowblock_fin_kernel<T, true, T> : sell_rowblock_fin_kernel<T, false, T>, cost_inv);
+    } else {  // point weights: the row_diag instances
+        using RD = row_diag<T>;
+        launch(pl.val22.get() ? sell_rowblock_fin_kernel<T, true, RD> : sell_rowblock_fin_kernel<T, false, RD>,
+               RD{ cost_inv, sinv });
+    }
     MI_LAUNCH_CHECK();
 }
 

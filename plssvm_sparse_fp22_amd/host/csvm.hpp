@@ -180,6 +180,10 @@ class csvm : public csvm_interface<T> {
         on_all([&](int, plssvm_mi_ctx *x) { return plssvm_mi_set_cost(x, (double) c); });
         this->cost_ = c;
     }
+    // empty: the context's weights are cleared (those of an earlier learn() must not reach a later call)
+    void apply_point_weights(const std::vector<T> &s) override {
+        on_all([&](int, plssvm_mi_ctx *x) { return plssvm_mi_set_point_weights(x, s.empty() ? nullptr : s.data()); });
+    }
     void set_QA_cost(T qa) {
         on_all([&](int, plssvm_mi_ctx *x) { return plssvm_mi_set_qa_cost(x, (double) qa); });
         this->QA_cost_ = qa;
@@ -203,17 +207,58 @@ class csvm : public csvm_interface<T> {
         std::vector<T> Y(K * n);
         for (size_t c = 0; c < K; ++c)
             for (size_t i = 0; i < n; ++i) Y[c * n + i] = p.class_labels[i] == cls[c] ? T(1) : T(-1);
+        // class weights: class c's problem weighs its own points (the positives) by w[c], every other point by 1
+        std::vector<T> S;
+        if (!this->class_weights_.empty()) {
+            S.assign(K * n, T(1));
+            for (const auto &kv : this->class_weights_) {
+                const auto it = std::lower_bound(cls.begin(), cls.end(), kv.first);
+                if (it == cls.end() || *it != kv.first)
+                    throw exception{ "class_weights: the label " + shortest(kv.first) + " does not occur in the data!" };
+                const size_t c = (size_t) (it - cls.begin());
+                for (size_t i = 0; i < n; ++i)
+                    if (p.class_labels[i] == kv.first) S[c * n + i] = kv.second;
+            }
+        }
         if (!on_device_) setup_data_on_device();
+        apply_point_weights({});  // the classes' weights travel in S; binary weights of an earlier learn() do not apply
+        learn_lanes(Y, K, imax, nullptr, S.empty() ? nullptr : S.data(), (int64_t) n);
+        classes_ = std::move(cls);
+    }
+    // learn() at every cost of `costs` (a search over C) in one plssvm_mi_learn_lanes call: row k of alphas() / biases()
+    // / iterations_multi() / residual_traces() is learn() at costs[k], with the class weights if any are set
+    void learn_costs(const std::vector<T> &costs) { learn_costs(costs, this->num_features_); }
+    void learn_costs(const std::vector<T> &costs, std::size_t imax) {
+        if (this->value_ptr_ == nullptr) throw exception{ "No labels given for training! Maybe the data is only usable for prediction?" };
+        if (costs.empty()) throw exception{ "learn_costs needs at least one cost" };
+        for (const T c : costs)
+            if (!(c > T(0)) || !std::isfinite(c)) throw exception{ "learn_costs: every cost must be a finite number > 0!" };
+        const std::vector<T> s = this->point_weights();
+        const size_t K = costs.size(), n = this->num_data_points_;
+        std::vector<T> Y(K * n);
+        for (size_t k = 0; k < K; ++k) std::copy(this->value_ptr_->begin(), this->value_ptr_->end(), Y.begin() + k * n);
+        if (!on_device_) setup_data_on_device();  // stored tiles and lanes of an earlier call are reused
+        apply_point_weights(s);                   // the class weights, or none
+        const std::vector<double> cd(costs.begin(), costs.end());
+        learn_lanes(Y, K, imax, cd.data(), nullptr, 0);
+        classes_.clear();
+        costs_ = costs;
+    }
+    const std::vector<T> &costs() const { return costs_; }
+
+  private:
+    // plssvm_mi_learn_lanes on every rank; the results of rank 0 into alphas_, biases_, iterations_multi_, traces_
+    void learn_lanes(const std::vector<T> &Y, size_t K, std::size_t imax, const double *costs, const T *S, int64_t lds) {
+        const size_t n = this->num_data_points_;
         const size_t R = (size_t) grp_->size();
         std::vector<std::vector<T>> al(R, std::vector<T>(K * n));
         std::vector<std::vector<double>> bi(R, std::vector<double>(K)), tr(R, std::vector<double>(K * (imax + 1), 0.0));
         std::vector<std::vector<int64_t>> its(R, std::vector<int64_t>(K, 0));
         on_all([&](int r, plssvm_mi_ctx *c) {
-            return plssvm_mi_learn_multi(c, Y.data(), (int64_t) K, (int64_t) n, (int64_t) imax, (double) this->epsilon_,
-                                         al[(size_t) r].data(), bi[(size_t) r].data(), tr[(size_t) r].data(),
-                                         its[(size_t) r].data());
+            return plssvm_mi_learn_lanes(c, Y.data(), (int64_t) K, (int64_t) n, costs, S, lds, (int64_t) imax,
+                                         (double) this->epsilon_, al[(size_t) r].data(), bi[(size_t) r].data(),
+                                         tr[(size_t) r].data(), its[(size_t) r].data());
         });
-        classes_ = std::move(cls);
         alphas_ = std::move(al[0]);
         biases_.assign(bi[0].begin(), bi[0].end());
         iterations_multi_ = std::move(its[0]);
@@ -221,6 +266,8 @@ class csvm : public csvm_interface<T> {
         for (size_t c = 0; c < K; ++c)
             traces_.emplace_back(tr[0].begin() + c * (imax + 1), tr[0].begin() + c * (imax + 1) + iterations_multi_[c] + 1);
     }
+
+  public:
     // the model of a one-vs-all model file: classes [K], alphas [K][n] (row-major), rhos [K]
     void set_model_multi(std::vector<T> classes, std::vector<T> alphas, const std::vector<T> &rhos) {
         if (classes.empty() || rhos.size() != classes.size() || alphas.size() != classes.size() * this->num_data_points_)
@@ -441,7 +488,7 @@ class csvm : public csvm_interface<T> {
     int64_t iterations_ = 0;
     bool on_device_ = false;
     // the one-vs-all model (learn_multi / set_model_multi)
-    std::vector<T> classes_, alphas_, biases_;
+    std::vector<T> classes_, alphas_, biases_, costs_;  // costs_: learn_costs' grid (then classes_ is empty)
     std::vector<int64_t> iterations_multi_;
     std::vector<std::vector<double>> traces_;
 };

@@ -18,6 +18,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
+#include <map>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -60,6 +61,17 @@ class csvm_interface {
     csvm_interface(const csvm_interface &) = delete;
     csvm_interface &operator=(const csvm_interface &) = delete;
 
+    // Class weights (build-defined; LIBSVM's -wi): the points of label L are trained at cost C * w[L], labels the map
+    // does not name at C. learn() and the backend's learn_multi() / learn_costs() honour them; only the diagonal of the
+    // system changes (1/C -> (1/C)(1/s_i)) and QA_cost = k(x_m, x_m) + (1/C)(1/s_m). An empty map clears them.
+    void set_class_weights(std::map<T, T> w) {
+        for (const auto &kv : w)
+            if (!(kv.second > T(0)) || !std::isfinite(kv.second))
+                throw exception{ "class_weights: the weight of a label must be a finite number > 0!" };
+        class_weights_ = std::move(w);
+    }
+    const std::map<T, T> &class_weights() const { return class_weights_; }
+
     // csvm<T>::learn (src/plssvm/csvm.cpp:207-267): setup, q, b = y[0..m) - y[m], QA_cost = k(x_m, x_m) + 1/C,
     // solver_CG with imax = num_features, bias = y[m] + QA_cost sum(alpha) - q^T alpha, alpha[m] = -sum(alpha)
     void learn() { learn(num_features_); }
@@ -69,13 +81,15 @@ class csvm_interface {
         if (value_ptr_->size() != num_data_points_)
             throw exception{ "Number of labels (" + std::to_string(value_ptr_->size()) +
                              ") must match the number of data points (" + std::to_string(num_data_points_) + ")!" };
+        const std::vector<T> sw = point_weights();  // checked before the device is touched
         setup_data_on_device();
+        apply_point_weights(sw);
         auto start = std::chrono::steady_clock::now();
         const std::vector<T> q = generate_q();
         std::vector<T> b(value_ptr_->begin(), value_ptr_->end() - 1);
         for (T &v : b) v -= value_ptr_->back();
         const std::vector<T> last = point(num_data_points_ - 1);
-        QA_cost_ = kernel_function(last, last) + T(1) / cost_;
+        QA_cost_ = kernel_function(last, last) + (sw.empty() ? T(1) / cost_ : (T(1) / cost_) * (T(1) / sw.back()));
         if (print_info_) {
             std::printf("Setup for solving the optimization problem done in %lldms.\n", (long long) ms_since(start));
             start = std::chrono::steady_clock::now();
@@ -98,6 +112,28 @@ class csvm_interface {
     static long long ms_since(std::chrono::steady_clock::time_point t) {
         return (long long) std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t).count();
     }
+
+    // the labels the class weights name: the values as written where the parameter set kept them, else the +-1 signs
+    [[nodiscard]] const std::vector<T> &weight_labels() const {
+        static const std::vector<T> none;
+        if (params_.class_labels.size() == num_data_points_) return params_.class_labels;
+        return value_ptr_ != nullptr ? *value_ptr_ : none;
+    }
+    // s[n] of the class weights for a binary problem (empty: none set); a label the data lacks is an error
+    [[nodiscard]] std::vector<T> point_weights() const {
+        if (class_weights_.empty()) return {};
+        const std::vector<T> &lab = weight_labels();
+        std::vector<T> s(lab.size(), T(1));
+        for (const auto &kv : class_weights_) {
+            bool hit = false;
+            for (std::size_t i = 0; i < lab.size(); ++i)
+                if (lab[i] == kv.first) s[i] = kv.second, hit = true;
+            if (!hit) throw exception{ "class_weights: the label " + shortest(kv.first) + " does not occur in the data!" };
+        }
+        return s;
+    }
+    // the backend hands s to the device after every setup (empty: it clears the device's weights)
+    virtual void apply_point_weights(const std::vector<real_type> &) {}
 
     // ---- pure virtual, implemented by every backend (include/plssvm/csvm.hpp:188-214) ----
     virtual void setup_data_on_device() = 0;
@@ -149,6 +185,7 @@ class csvm_interface {
     std::size_t num_features_{};
     real_type bias_{};
     real_type QA_cost_{};
+    std::map<real_type, real_type> class_weights_{};
     std::vector<real_type> w_{};
     parameter<T> params_;  // the parameter set itself (CSR arrays of sparse sets)
 };

@@ -5,8 +5,10 @@
 // Additions (not in the reference): --sparse keeps LIBSVM input as CSR (the reference densifies),
 // --max_iter overrides the CG limit (default: num_features, csvm.cpp:256), --single trains in fp32
 // (the reference selects that at compile time, main_train.cpp:21-25), --device picks the GPU, --multiclass trains
-// one-vs-all over the file's distinct labels (three or more) and writes the one-vs-all model file.
+// one-vs-all over the file's distinct labels (three or more) and writes the one-vs-all model file, --class_weights
+// L1:W1,L2:W2 trains the points of label Li at cost C * Wi (LIBSVM's -wi; with --multiclass: the positives of class Li).
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -45,7 +47,41 @@ const char *kHelp =
     "      --device arg           train on this one HIP device (default: every visible device)\n"
     "      --devices arg          comma-separated device list, one rank per entry (a device listed twice:\n"
     "                             in-process host exchange instead of RCCL)\n"
-    "      --multiclass           one-vs-all over the file's distinct labels (three or more classes)\n";
+    "      --multiclass           one-vs-all over the file's distinct labels (three or more classes)\n"
+    "      --class_weights arg    L1:W1,L2:W2,...: train the points of label Li at cost C * Wi, all others at C\n"
+    "                             (with --multiclass: the points of class Li in class Li's own problem)\n";
+
+// "L1:W1,L2:W2" -> {label: weight}; false (with the reason in why) for a malformed list or a weight that is not > 0
+template <typename T>
+bool parse_class_weights(const std::string &list, std::map<T, T> &out, std::string &why) {
+    out.clear();
+    for (size_t a = 0; a <= list.size();) {
+        const size_t b = std::min(list.find(',', a), list.size());
+        const std::string item = list.substr(a, b - a);
+        const size_t colon = item.find(':');
+        if (colon == std::string::npos || colon == 0 || colon + 1 >= item.size()) {
+            why = "'" + item + "' is not of the form label:weight";
+            return false;
+        }
+        char *e1 = nullptr, *e2 = nullptr;
+        const std::string ls = item.substr(0, colon), ws = item.substr(colon + 1);
+        const double l = std::strtod(ls.c_str(), &e1), w = std::strtod(ws.c_str(), &e2);
+        if (*e1 != '\0' || *e2 != '\0' || !std::isfinite(l)) {
+            why = "'" + item + "' is not of the form label:weight";
+            return false;
+        }
+        if (!(w > 0) || !std::isfinite(w) || !((T) w > T(0)) || !std::isfinite((T) w)) {
+            why = "the weight of label " + ls + " must be a finite number > 0, not " + ws;
+            return false;
+        }
+        if (!out.emplace((T) l, (T) w).second) {
+            why = "the label " + ls + " is listed twice";
+            return false;
+        }
+        a = b + 1;
+    }
+    return true;
+}
 
 template <typename T>
 int train(const cli &c) {
@@ -82,9 +118,24 @@ int train(const cli &c) {
         std::fprintf(stderr, "The laplacian kernel takes dense input: it cannot be combined with --sparse!\n");
         return EXIT_FAILURE;
     }
+    std::map<T, T> weights;
+    if (c.opt.count("class_weights")) {  // syntax and signs: before the file is read or a GPU touched
+        std::string why;
+        if (!parse_class_weights<T>(c.opt.at("class_weights"), weights, why)) {
+            std::fprintf(stderr, "--class_weights: %s!\n", why.c_str());
+            return EXIT_FAILURE;
+        }
+    }
     const auto t0 = std::chrono::steady_clock::now();
     const bool multiclass = c.opt.count("multiclass") > 0;
-    params.parse_train_file(c.pos[0], c.opt.count("sparse") > 0, multiclass);
+    // class weights name the labels as the file writes them: keep those values beside their signs
+    params.parse_train_file(c.pos[0], c.opt.count("sparse") > 0, multiclass || !weights.empty());
+    for (const auto &kv : weights)
+        if (std::find(params.class_labels.begin(), params.class_labels.end(), kv.first) == params.class_labels.end()) {
+            std::fprintf(stderr, "--class_weights: the label %s does not occur in '%s'!\n", csvm<T>::shortest(kv.first).c_str(),
+                         c.pos[0].c_str());
+            return EXIT_FAILURE;
+        }
     if (c.pos.size() > 1) params.model_filename = c.pos[1];
     if (multiclass) {
         std::vector<T> distinct = params.class_labels;
@@ -132,6 +183,7 @@ int train(const cli &c) {
         devs = csvm<T>::all_devices(params);
     }
     csvm<T> svm(params, devs);
+    svm.set_class_weights(weights);
     if (params.print_info) {
         std::printf("Found %d HIP device(s):\n", svm.num_devices());
         for (const int d : svm.devices()) std::printf("  [%d, gfx950]\n", d);
