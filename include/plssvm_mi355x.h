@@ -325,6 +325,39 @@ PLSSVM_MI_API int plssvm_mi_set_point_weights(plssvm_mi_ctx *ctx, const void *s)
 PLSSVM_MI_API int plssvm_mi_learn_lanes(plssvm_mi_ctx *ctx, const void *Y, int64_t nlane, int64_t ldy, const double *costs,
                                         const void *S, int64_t lds, int64_t imax, double eps, void *alpha_out,
                                         double *bias_out, double *delta_trace, int64_t *iters);
+/* Held-out points as lanes (k-fold cross-validation; build-defined): plssvm_mi_learn_lanes whose lane k also leaves
+ * out the points i with HOLD[k * ldh + i] != 0 (rows of n flags, ldh >= n apart; ldh == 0: one row serves every lane;
+ * HOLD NULL: this is plssvm_mi_learn_lanes). In this order, the contract:
+ *  1. The system. Lane k trains on T_k = the points not held out. With its pivot t (2.) and R_k = T_k \ {t} it solves
+ *     the principal submatrix on R_k of Q~_ij = k_ij + QA - q_i - q_j + delta_ij diag_i, q_i = k(x_i, x_t),
+ *     QA = k_tt + diag_t, right-hand side b_i = y_i - y_t, by the reference CG from x0 = 1 on R_k; then
+ *     alpha_t = -sum alpha, bias = y_t + QA sum alpha - sum_i q_i alpha_i: plssvm_mi_learn on the subset T_k.
+ *  2. The pivot t is the lane's largest training index (pivots[k], nullable output of nlane entries). t = n - 1 unless
+ *     the lane holds the last point out; such lanes share one extra product K e_t that yields their q.
+ *  3. alpha_out[k][i] is exactly 0 on every held-out point i.
+ *  4. A lane is BITWISE the call with that lane alone at PLSSVM_MI_OPT_MULTI_WIDTH = 1, whatever its position, the
+ *     other lanes, the width or the tile cache.
+ *  5. A lane whose hold row is all zero is BITWISE plssvm_mi_learn_lanes' lane (alpha, bias, iterations, trace).
+ *  6. Offered where the lanes share a pass over the kernel matrix: dense data (or sparse data on the densified path)
+ *     with the pairwise tile kernels, on one GPU, with the reference CG. A stored sparse setup, the factored linear
+ *     path, a group, a simulated rank or the one-reduction CG with a non-NULL HOLD: PLSSVM_MI_ERR_UNSUPPORTED,
+ *     plssvm_mi_last_error names the setup, the context stays usable.
+ * Other arguments and outputs as plssvm_mi_learn_lanes'. 0 < ldh < n, or a lane with fewer than two training points:
+ * PLSSVM_MI_ERR_ARG. The context's cost, weights and q are what they were when the call returns. */
+PLSSVM_MI_API int plssvm_mi_learn_held(plssvm_mi_ctx *ctx, const void *Y, int64_t nlane, int64_t ldy, const double *costs,
+                                       const void *S, int64_t lds, const uint8_t *HOLD, int64_t ldh, int64_t imax,
+                                       double eps, void *alpha_out, double *bias_out, double *delta_trace, int64_t *iters,
+                                       int64_t *pivots);
+/* Decision values of nclass models on the context's own n points (training and held-out alike):
+ * OUT[c][i] = bias[c] + sum_j ALPHA[c][j] k(x_j, x_i), i < n; ALPHA[nclass][lda], OUT[nclass][ldo], lda, ldo >= n. One
+ * pass over the kernel matrix per group of models where the lanes are batched, one per model elsewhere (dense and
+ * sparse setups, every K.p path, on one GPU); no point is uploaded or prepared again. Row c is bitwise the same whatever
+ * nclass, its position and the width. A context of a group (plssvm_mi_comm_init*) or with a simulated rank holds only
+ * its share of the product: PLSSVM_MI_ERR_UNSUPPORTED, the context stays usable. If the context's q is not the one
+ * plssvm_mi_generate_q forms (a caller's q from plssvm_mi_kp / _solve_cg), it is generated anew and replaces it; QA_cost
+ * is kept. */
+PLSSVM_MI_API int plssvm_mi_train_values(plssvm_mi_ctx *ctx, const void *ALPHA, int64_t nclass, int64_t lda,
+                                         const double *bias, void *OUT, int64_t ldo);
 /* Timing hook: plssvm_mi_time_kp's K·p time for the product with nrhs resident vectors (in groups of the width; one at
  * a time where nothing is batched), averaged over `reps` products, measured with hipEvents on the context's stream. */
 PLSSVM_MI_API int plssvm_mi_time_kp_multi(plssvm_mi_ctx *ctx, int64_t nrhs, int reps, double *ms_per_kp);

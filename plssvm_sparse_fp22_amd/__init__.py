@@ -149,6 +149,23 @@ def one_vs_all_weights(labels, class_weight, dtype=np.float64):
     return np.ascontiguousarray(S)
 
 
+def stratified_folds(labels, nfold):
+    """Fold of every point for k-fold cross-validation: point i goes to fold (its rank among the points of its label, in
+    index order) mod nfold. Every fold gets floor(c / nfold) or ceil(c / nfold) points of a label with c points. No
+    random numbers: the same labels give the same folds (plssvm-train -v uses the same rule)."""
+    labels = np.asarray(labels)
+    if labels.ndim != 1 or labels.size == 0:
+        raise ValueError("labels must be a non-empty 1-D array")
+    nfold = int(nfold)
+    if nfold < 2 or nfold > labels.size:
+        raise ValueError(f"nfold must be between 2 and the number of points ({labels.size}), not {nfold}")
+    folds = np.empty(labels.size, dtype=np.int64)
+    for lab in np.unique(labels):
+        idx = np.flatnonzero(labels == lab)
+        folds[idx] = np.arange(idx.size) % nfold
+    return folds
+
+
 def _rows(a, dtype, m, what):
     """[R][ld] row-major matrix of the real type with ld >= m (a 1-D vector counts as one row)."""
     a = np.ascontiguousarray(np.atleast_2d(a), dtype=dtype)
@@ -303,6 +320,8 @@ class CSVM:
         self.biases = None
         self.iters_multi = None
         self.traces = None
+        self.pivots = None  # learn_held: each lane's largest training index
+        self.cv_iters = None  # cross_validate: iterations per lane (lane = cost * nfold + fold)
         self._on_device = False
         self._cw_applied = False  # the context's weights are those of Parameter.class_weight (learn / learn_costs)
 
@@ -530,6 +549,110 @@ class CSVM:
         self._learn_lanes(Y, costs, None, imax)
         self.costs = costs
         return self
+
+    def learn_held(self, hold, costs=None, S=None, imax=-1):
+        """learn() on subsets, as lanes of one batched CG (plssvm_mi_learn_held): lane k leaves out the points with
+        hold[k][i] true (hold: bool [K][n]) and trains at costs[k] (None: the context's cost) with the weights S ([K][n],
+        one row [n] for all, or None: the context's). Sets alphas [K][n] (exactly 0 on held-out points), biases [K],
+        iters_multi, traces and pivots [K] (each lane's largest training index). Parameter.class_weight applies as in
+        learn_costs (a row of S replaces it for its lane); the context's cost and q stay."""
+        if self.params.labels is None:
+            raise ValueError("No labels given for training! Maybe the data is only usable for prediction?")
+        cw = self.params.point_weights()  # class_weight (checked before the device is touched)
+        n = self.num_data_points
+        H = np.ascontiguousarray(np.atleast_2d(np.asarray(hold)) != 0, dtype=np.uint8)
+        if H.ndim != 2 or H.shape[1] != n or H.shape[0] < 1:
+            raise ValueError(f"hold must be a [lanes][{n}] matrix")
+        K = H.shape[0]
+        if not self._on_device:
+            self.setup_data_on_device()
+        self._apply_class_weight(cw)
+        y = np.ascontiguousarray(self.params.labels, dtype=self.dtype)
+        Y = np.ascontiguousarray(np.tile(y, (K, 1)))
+        im = self.num_features if imax < 0 else imax
+        alphas = np.zeros((K, n), dtype=self.dtype)
+        biases = np.zeros(K, dtype=np.float64)
+        trace = np.full((K, im + 1), np.nan)
+        it = np.zeros(K, dtype=np.int64)
+        piv = np.zeros(K, dtype=np.int64)
+        cc = None if costs is None else np.ascontiguousarray(costs, dtype=np.float64)
+        SS = None if S is None else np.ascontiguousarray(S, dtype=self.dtype)
+        if cc is not None and cc.shape != (K,):
+            raise ValueError(f"costs must have {K} entries")
+        if SS is not None and SS.shape not in ((K, n), (n,)):
+            raise ValueError(f"the weights must be [{K}][{n}] or one row of {n}")
+        lds = 0 if SS is None or SS.ndim == 1 else SS.shape[1]
+        self._check(_abi.lib().plssvm_mi_learn_held(self._ctx, _ptr(Y), K, n, _ptr(cc), _ptr(SS), lds, _ptr(H), n, im,
+                                                    float(self.params.epsilon), _ptr(alphas), _ptr(biases), _ptr(trace),
+                                                    _ptr(it), _ptr(piv)))
+        self.alphas = alphas
+        self.biases = biases.astype(self.dtype)
+        self.iters_multi = it
+        self.traces = [trace[c, : it[c] + 1].copy() for c in range(K)]
+        self.pivots = piv
+        return self
+
+    def train_values(self, alphas=None, biases=None):
+        """Decision values [n][K] of K models (default: alphas, biases as the last multi-lane learn left them) on the
+        context's own n points, held-out ones included, from the kernel matrix the context already holds
+        (plssvm_mi_train_values): no point is uploaded again. Column k is bitwise the same whatever K."""
+        alphas = self.alphas if alphas is None else alphas
+        biases = self.biases if biases is None else biases
+        if alphas is None:
+            raise ValueError("No alphas provided!")
+        n = self.num_data_points
+        A = _rows(alphas, self.dtype, n, "alphas")
+        K, lda = A.shape
+        b = np.zeros(K, dtype=np.float64) if biases is None else np.ascontiguousarray(np.atleast_1d(biases), dtype=np.float64)
+        if b.shape != (K,):
+            raise ValueError(f"biases must have {K} entries")
+        if not self._on_device:
+            self.setup_data_on_device()
+        out = np.zeros((K, n), dtype=self.dtype)
+        self._check(_abi.lib().plssvm_mi_train_values(self._ctx, _ptr(A), K, lda, _ptr(b), _ptr(out), n))
+        return np.ascontiguousarray(out.T)
+
+    def cross_validate(self, nfold=5, costs=None, folds=None, imax=-1):
+        """k-fold cross-validation of the binary problem at every cost of `costs` (None: the parameter's cost), the
+        nfold x len(costs) subset problems as lanes of one batched CG over the setup's stored kernel matrix: learn_held,
+        then train_values, then each point's value from the model that did not see it. folds [n] (values 0 .. nfold - 1;
+        None: stratified_folds of the labels). Parameter.class_weight and set_point_weights apply as in learn_costs.
+        Returns (accuracy [len(costs)], held-out decision values [len(costs)][n], folds [n]); a value of exactly 0
+        counts as the negative label, as predict() has it. The context's cost, weights, q and the object's model
+        (alpha, bias, alphas, biases, ...) are what they were before the call."""
+        if self.params.labels is None:
+            raise ValueError("No labels given for training! Maybe the data is only usable for prediction?")
+        n = self.num_data_points
+        y = np.asarray(self.params.labels)
+        if folds is None:
+            folds = stratified_folds(y, nfold)
+        else:
+            folds = np.ascontiguousarray(folds, dtype=np.int64)
+            nfold = int(nfold)
+            if folds.shape != (n,) or folds.min() < 0 or folds.max() >= nfold or nfold < 2:
+                raise ValueError(f"folds must have {n} entries in 0 .. nfold - 1, nfold >= 2")
+        nfold = int(nfold)
+        cl = np.atleast_1d(np.asarray(self.params.cost if costs is None else costs, dtype=np.float64))
+        if cl.ndim != 1 or cl.size < 1 or not (np.isfinite(cl).all() and (cl > 0).all()):
+            raise ValueError("costs must be a non-empty list of finite numbers > 0")
+        self.params.point_weights()  # class_weight is checked before the device is touched; learn_held applies it
+        if not self._on_device:
+            self.setup_data_on_device()
+        hold = np.concatenate([folds[None, :] == np.arange(nfold)[:, None]] * cl.size, axis=0)  # lane = cost * nfold + fold
+        keep = {k: getattr(self, k, None) for k in ("alphas", "biases", "iters_multi", "traces", "pivots", "classes")}
+        try:
+            self.learn_held(hold, costs=np.repeat(cl, nfold), imax=imax)
+            vals = self.train_values()  # [n][lanes]
+            cv_iters = self.iters_multi
+        finally:
+            for k, v in keep.items():
+                setattr(self, k, v)
+        self.cv_iters = cv_iters
+        lane = np.arange(cl.size)[:, None] * nfold + folds[None, :]
+        held = np.ascontiguousarray(vals[np.arange(n)[None, :], lane])
+        pred = np.where(held > 0, 1, -1)
+        acc = (pred == np.where(y > 0, 1, -1)[None, :]).mean(axis=1)
+        return acc, held, folds
 
     def learn_multi(self, labels=None, imax=-1, class_weight=None):
         """One-vs-all training on K >= 2 classes (any integer or float labels; default: the parameter's labels): per

@@ -35,7 +35,7 @@ EXPORTS = (
     "plssvm_mi_kp_multi", "plssvm_mi_solve_cg_multi", "plssvm_mi_learn_multi", "plssvm_mi_time_kp_multi",
     "plssvm_mi_predict_multi_dense", "plssvm_mi_predict_multi_csr", "plssvm_mi_get_predict_stats",
     "plssvm_mi_get_kp_cache_narrow_tiles", "plssvm_mi_get_spmv_plan",
-    "plssvm_mi_set_point_weights", "plssvm_mi_learn_lanes",
+    "plssvm_mi_set_point_weights", "plssvm_mi_learn_lanes", "plssvm_mi_learn_held", "plssvm_mi_train_values",
 )
 # the one entry point a PLSSVM_MI_LIB build may lack (a build from before the narrow record form, loaded for an A/B
 # run): CSVM.info() then reports kp_cache_narrow_tiles = 0, which is what such a build stores
@@ -137,6 +137,8 @@ def _declare(L):
         "plssvm_mi_time_kp_multi": ([P, I64, I, PD], I),
         "plssvm_mi_set_point_weights": ([P, P], I),
         "plssvm_mi_learn_lanes": ([P, P, I64, I64, P, P, I64, I64, D, P, P, P, P], I),
+        "plssvm_mi_learn_held": ([P, P, I64, I64, P, P, I64, P, I64, I64, D, P, P, P, P, P], I),
+        "plssvm_mi_train_values": ([P, P, I64, I64, P, P, I64], I),
         "plssvm_mi_predict_multi_dense": ([P, P, I64, I64, P, P, I64, I64, P, I64], I),
         "plssvm_mi_predict_multi_csr": ([P, P, I64, I64, P, P, P, P, I, I64, I64, P, I64], I),
         "plssvm_mi_get_predict_stats": ([P, PI64], I),

@@ -94,6 +94,25 @@ __global__ __launch_bounds__(256) void cg_init_kernel(const T *__restrict__ b, i
 }
 
 template <typename T>
+__global__ __launch_bounds__(256) void cg_init_held_kernel(const T *__restrict__ b, const uint8_t *__restrict__ hold,
+                                                           int64_t m, T *__restrict__ x, T *__restrict__ r) {
+    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    x[i] = hold[i] != 0 ? T(0) : T(1);
+    r[i] = b[i];
+}
+
+// out_i = (raw_i + q_i alpha_m) + bias, the product rounded before the add (this file's contraction is off)
+template <typename T>
+__global__ __launch_bounds__(256) void train_values_fin_kernel(const T *__restrict__ raw, const T *__restrict__ q,
+                                                               T alpha_m, T bias, int64_t m, T *__restrict__ out) {
+    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const T t = q[i] * alpha_m;
+    out[i] = (raw[i] + t) + bias;
+}
+
+template <typename T>
 __global__ __launch_bounds__(256) void copy_kernel(const T *__restrict__ src, int64_t n, T *__restrict__ dst,
                                                    const cg_scalars<T> *status) {
     if (status != nullptr && status->converged) return;
@@ -137,7 +156,8 @@ constexpr int CG_PRE = 2;
 // slabs != null: raw_i = sum_{k < P} slabs[k * m + i], summed as panel_reduce_kernel does — from 0 in
 // panel order, and for P >= 16 (its split form) as four quarter sums of ceil(P / 4) panels combined
 // ((q0 + q1) + q2) + q3 — so Ad is bitwise the reduced pass output the other K·p calls see
-// DG = T: the scalar diagonal 1/C; DG = row_diag<T>: (1/C)(1/s_i) with point weights (kernels.hpp)
+// DG = T: the scalar diagonal 1/C; DG = row_diag<T>: (1/C)(1/s_i) with point weights; DG = row_diag_held<T>: as either,
+// held rows get Ad = 0 and add nothing to the partials (kernels.hpp)
 template <typename T, typename DG>
 __global__ __launch_bounds__(CG_NT) void cg_fin_dad_kernel(const T *__restrict__ raw, const T *__restrict__ slabs,
                                                          int64_t P, int64_t sstride, const T *__restrict__ q,
@@ -176,6 +196,10 @@ __global__ __launch_bounds__(CG_NT) void cg_fin_dad_kernel(const T *__restrict__
     if (blockIdx.x == 0 && threadIdx.x == 0) sc->sp = sp, sc->sqp = sqp;
     T s1 = 0;
     auto one = [&](int64_t i, T r_, T q_, T d_) {
+        if (held_at(cost_inv, i)) {  // row_diag_held only: no row of this lane's system, nothing for d.Ad
+            Ad[i] = T(0);
+            return;
+        }
         const T v = cg_fin_value(r_, q_, d_, sp, sqp, QA_cost, diag_at(cost_inv, i), raw_only);
         Ad[i] = v;
         s1 = cg_acc(s1, d_, v);
@@ -486,9 +510,13 @@ void launch_cg1_delta(const T *pset, int G, double *trace, int64_t trace_cap, cg
 
 template <typename T>
 void launch_cg_fin_dad(const T *raw, const T *slabs, int64_t P, int64_t sstride, const T *q, const T *d, const T *psum,
-                       int G, T QA_cost, T cost_inv, const T *sinv, int raw_only, int64_t m, T *Ad, T *pdad,
-                       cg_scalars<T> *sc, hipStream_t s) {
-    if (sinv == nullptr)
+                       int G, T QA_cost, T cost_inv, const T *sinv, const uint8_t *hold, int raw_only, int64_t m, T *Ad,
+                       T *pdad, cg_scalars<T> *sc, hipStream_t s) {
+    if (hold != nullptr)
+        hipLaunchKernelGGL((cg_fin_dad_kernel<T, row_diag_held<T>>), dim3(RED_BLOCKS), dim3(CG_NT), 0, s, raw, slabs, P,
+                           sstride, q, d, psum, G, QA_cost, row_diag_held<T>{ cost_inv, sinv, hold }, raw_only, m, Ad, pdad,
+                           sc);
+    else if (sinv == nullptr)
         hipLaunchKernelGGL((cg_fin_dad_kernel<T, T>), dim3(RED_BLOCKS), dim3(CG_NT), 0, s, raw, slabs, P, sstride, q, d,
                            psum, G, QA_cost, cost_inv, raw_only, m, Ad, pdad, sc);
     else
@@ -540,6 +568,21 @@ void launch_cg_init(const T *b, int64_t m, T *x, T *r, hipStream_t s) {
 }
 
 template <typename T>
+void launch_cg_init_held(const T *b, const uint8_t *hold, int64_t m, T *x, T *r, hipStream_t s) {
+    if (m <= 0) return;
+    hipLaunchKernelGGL(cg_init_held_kernel<T>, dim3((unsigned) ceil_div(m, 256)), dim3(256), 0, s, b, hold, m, x, r);
+    MI_LAUNCH_CHECK();
+}
+
+template <typename T>
+void launch_train_values_fin(const T *raw, const T *q, T alpha_m, T bias, int64_t m, T *out, hipStream_t s) {
+    if (m <= 0) return;
+    hipLaunchKernelGGL(train_values_fin_kernel<T>, dim3((unsigned) ceil_div(m, 256)), dim3(256), 0, s, raw, q, alpha_m,
+                       bias, m, out);
+    MI_LAUNCH_CHECK();
+}
+
+template <typename T>
 void launch_copy(const T *src, int64_t n, T *dst, const cg_scalars<T> *status, hipStream_t s) {
     if (n <= 0) return;
     hipLaunchKernelGGL(copy_kernel<T>, dim3((unsigned) ceil_div(n, 256)), dim3(256), 0, s, src, n, dst, status);
@@ -568,12 +611,15 @@ void launch_cg_direction(T *d, const T *r, int64_t m, const cg_scalars<T> *sc, h
     template void launch_dot_final<T>(const T *, cg_scalars<T> *, int, int64_t, double *, int64_t, T *,           \
                                       hipStream_t, int);                                                          \
     template void launch_cg_init<T>(const T *, int64_t, T *, T *, hipStream_t);                                   \
+    template void launch_cg_init_held<T>(const T *, const uint8_t *, int64_t, T *, T *, hipStream_t);            \
+    template void launch_train_values_fin<T>(const T *, const T *, T, T, int64_t, T *, hipStream_t);             \
     template void launch_copy<T>(const T *, int64_t, T *, const cg_scalars<T> *, hipStream_t);                    \
     template void launch_cg_update<T>(T *, T *, const T *, const T *, const T *, int, int64_t,                    \
                                       const cg_scalars<T> *, hipStream_t);                                        \
     template void launch_cg_direction<T>(T *, const T *, int64_t, const cg_scalars<T> *, hipStream_t);             \
     template void launch_cg_fin_dad<T>(const T *, const T *, int64_t, int64_t, const T *, const T *, const T *,    \
-                                       int, T, T, const T *, int, int64_t, T *, T *, cg_scalars<T> *, hipStream_t); \
+                                       int, T, T, const T *, const uint8_t *, int, int64_t, T *, T *, cg_scalars<T> *, \
+                                       hipStream_t);                                                                \
     template void launch_cg_upd_rr<T>(T *, T *, const T *, const T *, const T *, int, const T *, int, int64_t, T *, \
                                       cg_scalars<T> *, hipStream_t);                                                \
     template void launch_cg_dir_sums<T>(T *, const T *, const T *, const T *, int, int, double *, int64_t, int64_t, \

@@ -394,6 +394,26 @@ int plssvm_mi_learn_lanes(plssvm_mi_ctx *ctx, const void *Y, int64_t nlane, int6
     });
 }
 
+int plssvm_mi_learn_held(plssvm_mi_ctx *ctx, const void *Y, int64_t nlane, int64_t ldy, const double *costs, const void *S,
+                         int64_t lds, const uint8_t *HOLD, int64_t ldh, int64_t imax, double eps, void *alpha_out,
+                         double *bias_out, double *delta_trace, int64_t *iters, int64_t *pivots) {
+    if (!ctx || !Y || !alpha_out || nlane < 1) return PLSSVM_MI_ERR_ARG;
+    return ctx->call([&](auto &e) {
+        using T = std::remove_reference_t<decltype(e.gamma)>;
+        e.learn_held(static_cast<const T *>(Y), nlane, ldy, costs, static_cast<const T *>(S), lds, HOLD, ldh, imax, (T) eps,
+                     static_cast<T *>(alpha_out), bias_out, delta_trace, iters, pivots);
+    });
+}
+
+int plssvm_mi_train_values(plssvm_mi_ctx *ctx, const void *ALPHA, int64_t nclass, int64_t lda, const double *bias, void *OUT,
+                           int64_t ldo) {
+    if (!ctx || !ALPHA || !bias || !OUT || nclass < 1) return PLSSVM_MI_ERR_ARG;
+    return ctx->call([&](auto &e) {
+        using T = std::remove_reference_t<decltype(e.gamma)>;
+        e.train_values(static_cast<const T *>(ALPHA), nclass, lda, bias, static_cast<T *>(OUT), ldo);
+    });
+}
+
 int plssvm_mi_time_kp_multi(plssvm_mi_ctx *ctx, int64_t nrhs, int reps, double *ms_per_kp) {
     if (!ctx || nrhs < 1) return PLSSVM_MI_ERR_ARG;
     return ctx->call([&](auto &e) { e.time_kp_multi(nrhs, reps, ms_per_kp); });

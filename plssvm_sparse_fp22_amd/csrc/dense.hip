@@ -102,7 +102,8 @@ __global__ __launch_bounds__(256) void q_dense_kernel(kfun<T> kf, const T *__res
     }
 }
 
-// DG = T: the diagonal is the scalar 1/C; DG = row_diag<T>: (1/C)(1/s_i) with point weights (kernels.hpp)
+// DG = T: the diagonal is the scalar 1/C; DG = row_diag<T>: (1/C)(1/s_i) with point weights; DG = row_diag_held<T>: as
+// either, with T(0) stored on held rows (kernels.hpp)
 template <typename T, typename DG>
 __global__ __launch_bounds__(256) void kp_finalize_kernel(const T *__restrict__ raw, const T *__restrict__ q,
                                                           const T *__restrict__ p, const cg_scalars<T> *sc,
@@ -112,6 +113,10 @@ __global__ __launch_bounds__(256) void kp_finalize_kernel(const T *__restrict__ 
     if (status != nullptr && status->converged) return;
     const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
+    if (held_at(cost_inv, i)) {  // row_diag_held only: the row is not part of this lane's system
+        ret[i] = T(0);
+        return;
+    }
     const T sp = sc->sp, sqp = sc->sqp;
     // flags (overwrite): bit 0 = overwrite ret, bit 1 = raw share only (simulated rank != 0)
     const T v = (overwrite & 2) ? raw[i] : raw[i] + (QA_cost - q[i]) * sp - sqp + diag_at(cost_inv, i) * p[i];
@@ -194,10 +199,13 @@ void launch_q_dense(kfun<T> kf, const T *XT, int64_t n_pad, int64_t d, int64_t m
 
 template <typename T>
 void launch_kp_finalize(const T *raw, const T *q, const T *p, const cg_scalars<T> *sc, T QA_cost, T cost_inv,
-                        const T *sinv, T add, int overwrite, int64_t m, T *ret, const cg_scalars<T> *status,
-                        hipStream_t s) {
+                        const T *sinv, const uint8_t *hold, T add, int overwrite, int64_t m, T *ret,
+                        const cg_scalars<T> *status, hipStream_t s) {
     if (m <= 0) return;
-    if (sinv == nullptr)
+    if (hold != nullptr)
+        hipLaunchKernelGGL((kp_finalize_kernel<T, row_diag_held<T>>), dim3((unsigned) ceil_div(m, 256)), dim3(256), 0, s,
+                           raw, q, p, sc, QA_cost, row_diag_held<T>{ cost_inv, sinv, hold }, add, overwrite, m, ret, status);
+    else if (sinv == nullptr)
         hipLaunchKernelGGL((kp_finalize_kernel<T, T>), dim3((unsigned) ceil_div(m, 256)), dim3(256), 0, s, raw, q, p, sc,
                            QA_cost, cost_inv, add, overwrite, m, ret, status);
     else
@@ -229,7 +237,8 @@ void launch_gemv_n(const T *XT, int64_t n_pad, int64_t d, int64_t r0, int64_t r1
     template void launch_row_norms<T>(const T *, int64_t, int64_t, T *, hipStream_t);                            \
     template void launch_q_dense<T>(kfun<T>, const T *, int64_t, int64_t, int64_t, const T *, T *, hipStream_t); \
     template void launch_kp_finalize<T>(const T *, const T *, const T *, const cg_scalars<T> *, T, T, const T *, \
-                                        T, int, int64_t, T *, const cg_scalars<T> *, hipStream_t);               \
+                                        const uint8_t *, T, int, int64_t, T *, const cg_scalars<T> *,            \
+                                        hipStream_t);                                                            \
     template void launch_gemv_t<T>(const T *, int64_t, int64_t, int64_t, int64_t, const T *, T *,                \
                                    const cg_scalars<T> *, hipStream_t);                                          \
     template void launch_gemv_n<T>(const T *, int64_t, int64_t, int64_t, int64_t, const T *, T *,                \

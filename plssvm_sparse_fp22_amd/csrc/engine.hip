@@ -575,8 +575,8 @@ void engine<T>::kp_slab_reduce(const cg_lane &L, const cg_scalars<T> *status) {
 template <typename T>
 void engine<T>::kp_fin(const cg_lane &L, const T *p, T *out, T add, bool overwrite, const cg_scalars<T> *status) {
     const int flags = (overwrite ? 1 : 0) | ((sim_world > 0 && sim_rank != 0 && !shard) ? 2 : 0);
-    launch_kp_finalize<T>(L.raw + v0, qf() + v0, p + v0, L.sc, L.QA, L.cost_inv, L.sinv ? L.sinv + v0 : nullptr, add, flags,
-                          vn, out + v0, status, stream);
+    launch_kp_finalize<T>(L.raw + v0, qf() + v0, p + v0, L.sc, L.QA, L.cost_inv, L.sinv ? L.sinv + v0 : nullptr,
+                          L.hold ? L.hold + v0 : nullptr, add, flags, vn, out + v0, status, stream);
 }
 
 // out = (overwrite ? 0 : out) + add * Q~ p   — run_device_kernel + device_reduction
@@ -675,7 +675,8 @@ template <typename T>
 void engine<T>::cg_fin_dad(const cg_lane &L, const T *v, T *pd, const T *slabs, int64_t P) {
     const int raw_only = (sim_world > 0 && sim_rank != 0 && !shard) ? 1 : 0;
     launch_cg_fin_dad<T>(L.raw + v0, slabs, P, m, qf() + v0, v + v0, gathered ? cgp_g.get() : L.cgp, G, L.QA, L.cost_inv,
-                         L.sinv ? L.sinv + v0 : nullptr, raw_only, vn, L.Ad + v0, pd, L.sc, stream);
+                         L.sinv ? L.sinv + v0 : nullptr, L.hold ? L.hold + v0 : nullptr, raw_only, vn, L.Ad + v0, pd, L.sc,
+                         stream);
 }
 
 // alpha = delta / (d . Ad) (:116); x += alpha d; r = b every 50th iteration, else r -= alpha Ad   (:119-132)
@@ -721,7 +722,8 @@ void engine<T>::cg_begin(const T *b_host, const T *q_host, T eps, bool force, do
     graph_reset();  // QA_cost, trace and the vectors' contents may differ from the captured solve
     if (m > 0) MI_HIP_CHECK(hipMemcpyAsync(b.get(), b_host, sizeof(T) * (size_t) m, hipMemcpyHostToDevice, stream));
     // x = 1; r = b; r -= Q~x   (csvm.cpp:85-90)
-    launch_cg_init<T>(b.get(), m, x.get(), r.get(), stream);
+    if (hold_cur != nullptr) launch_cg_init_held<T>(b.get(), hold_cur, m, x.get(), r.get(), stream);  // learn_held's lane
+    else launch_cg_init<T>(b.get(), m, x.get(), r.get(), stream);
     kp_device(x.get(), r.get(), T(-1), false, nullptr);
     cg_delta0(own_lane());
     if (cg1) {
@@ -1099,15 +1101,15 @@ void engine<T>::need_pool() {
 }
 
 template <typename T>
-int64_t engine<T>::lane_bytes(bool with_sinv) const {
+int64_t engine<T>::lane_bytes(bool with_sinv, bool with_hold) const {
     return ((int64_t) (LV_COUNT + (with_sinv ? 1 : 0)) * q.size() + kp_wgs * KP_REC + 8 * RED_BLOCKS) * (int64_t) sizeof(T) +
-           (int64_t) sizeof(cg_scalars<T>);
+           (int64_t) sizeof(cg_scalars<T>) + (with_hold ? q.size() : 0);
 }
 
 // Lanes are taken from what the setup (tile cache included) left free, keeping 256 MiB for the single path's own
 // later needs (traces, a captured block): the widest of W, W / 2, ... that fits; 1 = not even two lanes fit.
 template <typename T>
-int engine<T>::multi_width_next(bool with_sinv) const {
+int engine<T>::multi_width_next(bool with_sinv, bool with_hold) const {
     if (!multi_batched()) return 1;
     if (lanes.width > 0) return lanes.width;
     size_t free_b = 0, total_b = 0;
@@ -1115,15 +1117,15 @@ int engine<T>::multi_width_next(bool with_sinv) const {
     MI_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
     const int64_t room = (int64_t) free_b - ((int64_t) 256 << 20);
     int w = multi_opt >= 2 ? std::min(multi_opt, KP_MULTI_W) : KP_MULTI_W;
-    while (w >= 2 && (int64_t) w * lane_bytes(with_sinv) > room) w /= 2;
+    while (w >= 2 && (int64_t) w * lane_bytes(with_sinv, with_hold) > room) w /= 2;
     return std::max(w, 1);
 }
 
 template <typename T>
-int engine<T>::multi_lanes(bool with_sinv) {
+int engine<T>::multi_lanes(bool with_sinv, bool with_hold) {
     if (!multi_batched()) return 1;
     if (lanes.width > 0) return lanes.width;
-    for (int w = multi_width_next(with_sinv); w >= 2; w /= 2) {
+    for (int w = multi_width_next(with_sinv, with_hold); w >= 2; w /= 2) {
         try {
             lanes.vstride = q.size();
             lanes.sstride = kp_wgs * KP_REC;
@@ -1132,6 +1134,7 @@ int engine<T>::multi_lanes(bool with_sinv) {
             lanes.part.alloc((int64_t) w * 8 * RED_BLOCKS, stream);
             lanes.sc.alloc(w, stream);
             if (with_sinv) lanes.sinv.alloc((int64_t) w * lanes.vstride, stream);
+            if (with_hold) lanes.hold.alloc((int64_t) w * lanes.vstride, stream);
             lanes.width = w;
             lanes_own_diag();
             return w;
@@ -1163,8 +1166,23 @@ bool engine<T>::need_lane_sinv() {
 }
 
 template <typename T>
+bool engine<T>::need_lane_hold() {
+    if (lanes.width < 2) return false;
+    if (lanes.hold.size() >= (int64_t) lanes.width * lanes.vstride) return true;
+    try {
+        lanes.hold.alloc((int64_t) lanes.width * lanes.vstride, stream);
+    } catch (const mi_error &e) {
+        if (e.code != -4) throw;
+        (void) hipGetLastError();
+        lanes.hold.reset();
+        return false;
+    }
+    return true;
+}
+
+template <typename T>
 void engine<T>::lanes_own_diag() {
-    lanes.diag.assign((size_t) std::max(lanes.width, 0), lane_diag{ cost_inv(), QAf(), sinv_dev() });
+    lanes.diag.assign((size_t) std::max(lanes.width, 0), lane_diag{ cost_inv(), QAf(), sinv_dev(), nullptr });
 }
 
 // One pass over the tiles for the vectors `kind` of lanes [c0, c0 + nvec); flags: the lanes' stop flags apply.
@@ -1209,7 +1227,7 @@ void engine<T>::cg_iter_multi(int nvec, int reset) {
 // solve_cg for nvec <= width right-hand sides (B[c * ld + i]) as lanes 0 .. nvec - 1; q is set
 template <typename T>
 void engine<T>::solve_cg_group(const T *B, int nvec, int64_t ld, int64_t imax, T eps, T *X_out, double *trace_out,
-                               int64_t *iters) {
+                               int64_t *iters, bool held) {
     need_pool();
     // cg_begin per lane
     const cg_scalars<T> init = cg_scalars_init(eps, false);
@@ -1224,18 +1242,26 @@ void engine<T>::solve_cg_group(const T *B, int nvec, int64_t ld, int64_t imax, T
     }
     for (int c = 0; c < nvec; ++c) {
         MI_HIP_CHECK(hipMemcpyAsync(lane_v(LV_B, c), B + c * ld, sizeof(T) * (size_t) m, hipMemcpyHostToDevice, stream));
-        launch_cg_init<T>(lane_v(LV_B, c), m, lane_v(LV_X, c), lane_v(LV_R, c), stream);  // x = 1; r = b
+        if (held) launch_cg_init_held<T>(lane_v(LV_B, c), lanes.diag[(size_t) c].hold, m, lane_v(LV_X, c), lane_v(LV_R, c), stream);
+        else launch_cg_init<T>(lane_v(LV_B, c), m, lane_v(LV_X, c), lane_v(LV_R, c), stream);  // x = 1; r = b
     }
-    // r -= Q~x: x0 = 1 is the same for every lane, so kp_device's first half runs once, on the engine's own buffers
-    // (sum p, sum q p in sc, the pairwise part in raw; with no stop flag it also fills an unfilled tile cache)
-    MI_HIP_CHECK(hipMemsetAsync(sc.get(), 0, sizeof(cg_scalars<T>), stream));
-    kp_sums(lane_v(LV_X, 0), own_lane(), nullptr);
-    kp_raw(lane_v(LV_X, 0), nullptr);
+    if (held) {
+        // x0 = 1 on the lane's own active rows: r -= Q~x per lane, one pass over the (filled) tiles for the group
+        kp_lanes(LV_X, LV_R, 0, nvec, T(-1), false, false);
+    } else {
+        // r -= Q~x: x0 = 1 is the same for every lane, so kp_device's first half runs once, on the engine's own buffers
+        // (sum p, sum q p in sc, the pairwise part in raw; with no stop flag it also fills an unfilled tile cache)
+        MI_HIP_CHECK(hipMemsetAsync(sc.get(), 0, sizeof(cg_scalars<T>), stream));
+        kp_sums(lane_v(LV_X, 0), own_lane(), nullptr);
+        kp_raw(lane_v(LV_X, 0), nullptr);
+    }
     for (int c = 0; c < nvec; ++c) {
         const cg_lane L = pool_lane(c);
-        cg_lane S = own_lane();  // the shared raw and sums, the lane's diagonal
-        S.cost_inv = L.cost_inv, S.QA = L.QA, S.sinv = L.sinv;
-        kp_fin(S, L.x, L.r, T(-1), false, nullptr);
+        if (!held) {
+            cg_lane S = own_lane();  // the shared raw and sums, the lane's diagonal
+            S.cost_inv = L.cost_inv, S.QA = L.QA, S.sinv = L.sinv;
+            kp_fin(S, L.x, L.r, T(-1), false, nullptr);
+        }
         cg_delta0(L);
         cg_dir(L, 1);
     }
@@ -1369,10 +1395,10 @@ void engine<T>::set_point_weights(const T *s) {
     set_sinv(inv);
 }
 
+// What learn_lanes and learn_held check of their common arguments, and the lanes' costs in T (costs null: the engine's)
 template <typename T>
-void engine<T>::learn_lanes(const T *Y, int64_t nlane, int64_t ldy, const double *costs, const T *S, int64_t lds,
-                            int64_t imax, T eps, T *alpha_out, double *bias_out, double *trace_out, int64_t *iters) {
-    need_data();
+std::vector<T> engine<T>::check_lane_args(const T *Y, int64_t nlane, int64_t ldy, const double *costs, const T *S,
+                                          int64_t lds) const {
     if (Y == nullptr) throw mi_error(-1, "No labels given for training! Maybe the data is only usable for prediction?");
     if (nlane < 1) throw mi_error(-1, "at least one class is needed");
     if (ldy < n) throw mi_error(-1, "the leading dimension is smaller than the number of points");
@@ -1385,14 +1411,26 @@ void engine<T>::learn_lanes(const T *Y, int64_t nlane, int64_t ldy, const double
                 throw mi_error(-1, "cost " + std::to_string(k) + " is not a finite number > 0");
             cost_k[(size_t) k] = c;
         }
-    const bool per_lane = S != nullptr && lds != 0;
     if (S != nullptr)
-        for (int64_t k = 0; k < (per_lane ? nlane : 1); ++k) check_weights(S + k * lds, n);
-    auto recip = [&](const T *s) {
-        std::vector<T> inv((size_t) n);
-        for (int64_t i = 0; i < n; ++i) inv[(size_t) i] = T(1) / s[i];
-        return inv;
-    };
+        for (int64_t k = 0; k < (lds != 0 ? nlane : 1); ++k) check_weights(S + k * lds, n);
+    return cost_k;
+}
+
+// the n reciprocals of a weight row
+template <typename T>
+std::vector<T> engine<T>::recip_weights(const T *s) const {
+    std::vector<T> inv((size_t) n);
+    for (int64_t i = 0; i < n; ++i) inv[(size_t) i] = T(1) / s[i];
+    return inv;
+}
+
+template <typename T>
+void engine<T>::learn_lanes(const T *Y, int64_t nlane, int64_t ldy, const double *costs, const T *S, int64_t lds,
+                            int64_t imax, T eps, T *alpha_out, double *bias_out, double *trace_out, int64_t *iters) {
+    need_data();
+    const std::vector<T> cost_k = check_lane_args(Y, nlane, ldy, costs, S, lds);
+    const bool per_lane = S != nullptr && lds != 0;
+    auto recip = [&](const T *s) { return recip_weights(s); };
     MI_HIP_CHECK(hipSetDevice(device));
     const T cost0 = cost;
     const std::vector<T> sinv0 = sinv_h;
@@ -1445,7 +1483,7 @@ void engine<T>::learn_lanes(const T *Y, int64_t nlane, int64_t ldy, const double
                     dm = cinv * sinv_h[(size_t) m];
                 }
                 QA[(size_t) k] = ctr_kmm + dm;
-                lanes.diag[(size_t) c] = lane_diag{ cinv, QA[(size_t) k], sv };
+                lanes.diag[(size_t) c] = lane_diag{ cinv, QA[(size_t) k], sv, nullptr };
             }
             solve_cg_group(bh.data() + c0 * ldy, nvec, ldy, imax, eps, alpha_out + c0 * ldy,
                            trace_out ? trace_out + c0 * cap : nullptr, iters ? iters + c0 : nullptr);
@@ -1473,6 +1511,272 @@ void engine<T>::learn_lanes(const T *Y, int64_t nlane, int64_t ldy, const double
         throw;
     }
     restore();
+}
+
+// ---- held-out points as masked lanes (engine.hpp) ---------------------------------------------------
+// Where the finalize is kp_finalize_kernel / cg_fin_dad_kernel and nothing else: the pairwise tile path on one rank with
+// the reference recurrence (multi_batched() without its width option)
+template <typename T>
+bool engine<T>::held_supported() const {
+    const bool tiles_path = !factored() && (!sparse || csr.dense_on);
+    return have_data && tiles_path && m > 0 && kp_wgs > 0 && world == 1 && comm == nullptr && xchg == nullptr &&
+           sim_world == 0 && !shard && !cg1_wanted();
+}
+
+template <typename T>
+void engine<T>::learn_held(const T *Y, int64_t nlane, int64_t ldy, const double *costs, const T *S, int64_t lds,
+                           const uint8_t *HOLD, int64_t ldh, int64_t imax, T eps, T *alpha_out, double *bias_out,
+                           double *trace_out, int64_t *iters, int64_t *pivots_out) {
+    need_data();
+    if (HOLD == nullptr) {
+        learn_lanes(Y, nlane, ldy, costs, S, lds, imax, eps, alpha_out, bias_out, trace_out, iters);
+        if (pivots_out) std::fill(pivots_out, pivots_out + nlane, m);
+        return;
+    }
+    const std::vector<T> cost_k = check_lane_args(Y, nlane, ldy, costs, S, lds);
+    const bool per_lane = S != nullptr && lds != 0;
+    if (ldh != 0 && ldh < n) throw mi_error(-1, "the hold rows' leading dimension is smaller than the number of points");
+    if (!held_supported()) {
+        const char *why = sparse_stored()              ? "a stored sparse setup"
+                          : factored()                 ? "the factored linear path"
+                          : (sim_world > 0)            ? "a simulated rank"
+                          : (world > 1 || comm != nullptr || xchg != nullptr || shard) ? "a multi-GPU group"
+                          : cg1_wanted()               ? "the one-reduction CG"
+                                                       : "a setup without kernel-matrix tiles";
+        throw mi_error(-5, std::string("held-out lanes run on the pairwise tile path of one GPU with the reference CG; this "
+                                       "context is ") + why + " (train on the subset with a fresh setup instead)");
+    }
+    // the pivots: the largest training index of every lane; lanes by pivot, pivot m first, then by first appearance
+    std::vector<int64_t> piv((size_t) nlane);
+    std::vector<int64_t> pivot_order;
+    for (int64_t k = 0; k < nlane; ++k) {
+        const uint8_t *h = HOLD + k * ldh;
+        int64_t t = -1, cnt = 0;
+        for (int64_t i = 0; i < n; ++i)
+            if (h[i] == 0) t = i, ++cnt;
+        if (cnt < 2) throw mi_error(-1, "lane " + std::to_string(k) + " has fewer than two training points");
+        piv[(size_t) k] = t;
+        if (std::find(pivot_order.begin(), pivot_order.end(), t) == pivot_order.end()) pivot_order.push_back(t);
+    }
+    std::stable_partition(pivot_order.begin(), pivot_order.end(), [&](int64_t t) { return t == m; });
+    if (pivots_out) std::copy(piv.begin(), piv.end(), pivots_out);
+    auto recip = [&](const T *s) { return recip_weights(s); };
+    MI_HIP_CHECK(hipSetDevice(device));
+    const T cost0 = cost;
+    const std::vector<T> sinv0 = sinv_h;
+    bool cost_touched = false, sinv_touched = false, q_touched = false;
+    auto run = [&]() {
+        if (S != nullptr && !per_lane) {
+            sinv_touched = true;
+            set_sinv(recip(S));
+        }
+        std::vector<T> qm(std::max<int64_t>(m, 1)), qt;
+        generate_q(qm.data(), nullptr);
+        if (imax < 0) imax = d;
+        const int64_t cap = imax + 1;
+        const int W = nlane == 1 ? 1 : multi_lanes(per_lane, true);
+        const bool batched = W >= 2 && need_lane_hold() && (!per_lane || need_lane_sinv());
+        if (hold_own.size() < q.size()) hold_own.alloc(q.size(), stream);
+        if (batched) {
+            need_pool();
+            if (kc.tiles > 0 && !kc.valid) {  // the batched launch streams filled records only: one single-path pass fills them
+                MI_HIP_CHECK(hipMemsetAsync(sc.get(), 0, sizeof(cg_scalars<T>), stream));
+                MI_HIP_CHECK(hipMemsetAsync(pv.get(), 0, sizeof(T) * (size_t) pv.size(), stream));
+                kp_raw(pv.get(), nullptr);
+            }
+        }
+        cg_active = false;
+        for (const int64_t t : pivot_order) {
+            std::vector<int64_t> ks;
+            for (int64_t k = 0; k < nlane; ++k)
+                if (piv[(size_t) k] == t) ks.push_back(k);
+            const T *qh = qm.data();
+            T ktt = ctr_kmm;
+            if (t != m) {
+                // q = column t of the kernel matrix: K e_t over the tiles, as kp_part forms it
+                const T one = T(1);
+                MI_HIP_CHECK(hipMemsetAsync(sc.get(), 0, sizeof(cg_scalars<T>), stream));
+                MI_HIP_CHECK(hipMemsetAsync(pv.get(), 0, sizeof(T) * (size_t) pv.size(), stream));
+                MI_HIP_CHECK(hipMemcpyAsync(pv.get() + t, &one, sizeof(T), hipMemcpyHostToDevice, stream));
+                q_touched = true;
+                kp_raw(pv.get(), nullptr);
+                MI_HIP_CHECK(hipMemcpyAsync(q.get(), raw.get(), sizeof(T) * (size_t) m, hipMemcpyDeviceToDevice, stream));
+                qt.resize((size_t) m);
+                MI_HIP_CHECK(hipMemcpyAsync(qt.data(), raw.get(), sizeof(T) * (size_t) m, hipMemcpyDeviceToHost, stream));
+                MI_HIP_CHECK(hipStreamSynchronize(stream));
+                q_gen = false;
+                graph_reset();
+                qh = qt.data();
+                ktt = qt[(size_t) t];
+            }
+            // a lane's mask (rows that are no part of its system: held, or from the pivot on), b and QA
+            const int64_t nk = (int64_t) ks.size();
+            std::vector<uint8_t> mask((size_t) (nk * m));
+            // rows n apart (not the caller's ldy): the host memory of a pivot's lanes does not grow with ldy
+            std::vector<T> bh((size_t) (nk * n), T(0)), xt((size_t) (nk * n), T(0)), QA((size_t) nk);
+            std::vector<double> tr(trace_out ? (size_t) (nk * cap) : 0);
+            std::vector<int64_t> it((size_t) nk);
+            std::vector<std::vector<T>> inv((size_t) nk);
+            for (int64_t j = 0; j < nk; ++j) {
+                const int64_t k = ks[(size_t) j];
+                const uint8_t *h = HOLD + k * ldh;
+                const T *y = Y + k * ldy;
+                for (int64_t i = 0; i < m; ++i) {
+                    const bool off = h[i] != 0 || i >= t;
+                    mask[(size_t) (j * m + i)] = off ? 1 : 0;
+                    bh[(size_t) (j * n + i)] = off ? T(0) : y[i] - y[t];
+                }
+                const T cinv = T(1) / cost_k[(size_t) k];
+                T dt = cinv;
+                if (per_lane) {
+                    inv[(size_t) j] = recip(S + k * lds);
+                    dt = cinv * inv[(size_t) j][(size_t) t];
+                } else if (weighted()) {
+                    dt = cinv * sinv_h[(size_t) t];
+                }
+                QA[(size_t) j] = ktt + dt;
+            }
+            if (batched) {
+                for (int64_t j0 = 0; j0 < nk; j0 += W) {
+                    const int nvec = (int) std::min<int64_t>(W, nk - j0);
+                    for (int c = 0; c < nvec; ++c) {
+                        const int64_t j = j0 + c;
+                        const T *sv = sinv_dev();
+                        if (per_lane) {
+                            MI_HIP_CHECK(hipMemcpyAsync(lane_sinv(c), inv[(size_t) j].data(), sizeof(T) * (size_t) m, hipMemcpyHostToDevice, stream));
+                            sv = lane_sinv(c);
+                        }
+                        MI_HIP_CHECK(hipMemcpyAsync(lane_hold(c), mask.data() + j * m, (size_t) m, hipMemcpyHostToDevice, stream));
+                        lanes.diag[(size_t) c] = lane_diag{ T(1) / cost_k[(size_t) ks[(size_t) j]], QA[(size_t) j], sv, lane_hold(c) };
+                    }
+                    solve_cg_group(bh.data() + j0 * n, nvec, n, imax, eps, xt.data() + j0 * n,
+                                   trace_out ? tr.data() + j0 * cap : nullptr, it.data() + j0, true);
+                }
+                lanes_own_diag();  // no later group meets this call's hold rows
+            } else {
+                for (int64_t j = 0; j < nk; ++j) {
+                    const int64_t k = ks[(size_t) j];
+                    cost_touched = cost_touched || costs != nullptr;
+                    cost = cost_k[(size_t) k];
+                    if (per_lane) {
+                        sinv_touched = true;
+                        set_sinv(inv[(size_t) j]);
+                    }
+                    QA_cost = QA[(size_t) j];
+                    cost_touched = true;  // QA_cost is this lane's pivot's
+                    MI_HIP_CHECK(hipMemcpyAsync(hold_own.get(), mask.data() + j * m, (size_t) m, hipMemcpyHostToDevice, stream));
+                    hold_cur = hold_own.get();
+                    solve_cg(bh.data() + j * n, nullptr, imax, eps, xt.data() + j * n, trace_out ? tr.data() + j * cap : nullptr,
+                             it.data() + j);
+                    hold_cur = nullptr;
+                    graph_reset();
+                }
+            }
+            // learn()'s end with t in the last point's part, in the caller's lane order
+            for (int64_t j = 0; j < nk; ++j) {
+                const int64_t k = ks[(size_t) j];
+                T *a = alpha_out + k * ldy;
+                std::copy(xt.begin() + j * n, xt.begin() + j * n + m, a);
+                a[m] = T(0);
+                if (t == m) {
+                    learn_tail(Y + k * ldy, qh, QA[(size_t) j], a, bias_out ? bias_out + k : nullptr);
+                } else {
+                    T s = 0, qa = 0;
+                    for (int64_t i = 0; i < m; ++i) s += a[i];
+                    for (int64_t i = 0; i < m; ++i) qa = std::fma(qh[i], a[i], qa);
+                    const T bias = Y[k * ldy + t] + QA[(size_t) j] * s - qa;
+                    a[t] = -s;
+                    if (bias_out) bias_out[k] = (double) bias;
+                }
+                if (iters) iters[k] = it[(size_t) j];
+                if (trace_out) std::copy(tr.begin() + j * cap, tr.begin() + (j + 1) * cap, trace_out + k * cap);
+            }
+        }
+    };
+    auto restore = [&]() {
+        hold_cur = nullptr;
+        cost = cost0;
+        if (lanes.width >= 2) lanes_own_diag();
+        if (sinv_touched) set_sinv(sinv0);
+        if (q_touched) generate_q(nullptr, nullptr);  // the last point's q and the QA_cost of the restored diagonal
+        else if (cost_touched && !sinv_touched) QA_cost = ctr_kmm + diag_m();  // generate_q's (it ran before the cost moved)
+        graph_reset();
+    };
+    try {
+        run();
+    } catch (...) {
+        try {
+            restore();
+        } catch (...) {
+        }
+        throw;
+    }
+    restore();
+}
+
+template <typename T>
+void engine<T>::train_values(const T *ALPHA, int64_t nclass, int64_t lda, const double *bias, T *OUT, int64_t ldo) {
+    need_data();
+    if (ALPHA == nullptr || OUT == nullptr || bias == nullptr) throw mi_error(-1, "train_values needs alpha, bias and an output");
+    if (nclass < 1) throw mi_error(-1, "at least one model is needed");
+    if (lda < n || ldo < n) throw mi_error(-1, "a leading dimension is smaller than the number of points");
+    // a simulated rank's K·p is its share only, and a group's ranks would each need the others' rows of q and alpha
+    if (sim_world > 0 || world > 1 || comm != nullptr || xchg != nullptr || shard)
+        throw mi_error(-5, std::string("train_values runs on one GPU; this context is ") +
+                               (sim_world > 0 ? "a simulated rank" : "part of a multi-GPU group") + " (predict on the points instead)");
+    MI_HIP_CHECK(hipSetDevice(device));
+    if (!(have_q && q_gen) || (int64_t) q_gen_h.size() != m) {
+        // a caller's q is replaced by the generated one; a QA_cost in place (plssvm_mi_set_qa_cost) stays
+        const bool had = have_q;
+        const T qa0 = QA_cost;
+        generate_q(nullptr, nullptr);
+        if (had) QA_cost = qa0;
+    }
+    cg_active = false;
+    // the last point: sum_j q_j alpha_j as an fma chain in index order (learn_tail's), then k_mm alpha_m, then the bias
+    for (int64_t c = 0; c < nclass; ++c) {
+        const T *a = ALPHA + c * lda;
+        T acc = 0;
+        for (int64_t j = 0; j < m; ++j) acc = std::fma(q_gen_h[(size_t) j], a[j], acc);
+        const T last = ctr_kmm * a[m];
+        OUT[c * ldo + m] = (acc + last) + (T) bias[c];
+    }
+    if (m <= 0) return;
+    const int W = nclass == 1 ? 1 : multi_lanes();
+    if (W < 2) {  // one vector after another: kp_part's K·p, then the finalize
+        for (int64_t c = 0; c < nclass; ++c) {
+            const T *a = ALPHA + c * lda;
+            MI_HIP_CHECK(hipMemsetAsync(sc.get(), 0, sizeof(cg_scalars<T>), stream));
+            MI_HIP_CHECK(hipMemcpyAsync(pv.get(), a, sizeof(T) * (size_t) m, hipMemcpyHostToDevice, stream));
+            kp_raw(pv.get(), nullptr);
+            launch_train_values_fin<T>(raw.get(), q.get(), a[m], (T) bias[c], m, ret.get(), stream);
+            MI_HIP_CHECK(hipMemcpyAsync(OUT + c * ldo, ret.get(), sizeof(T) * (size_t) m, hipMemcpyDeviceToHost, stream));
+            MI_HIP_CHECK(hipStreamSynchronize(stream));
+        }
+        return;
+    }
+    need_pool();
+    for (int64_t c0 = 0; c0 < nclass; c0 += W) {
+        const int nvec = (int) std::min<int64_t>(W, nclass - c0);
+        for (int c = 0; c < nvec; ++c)
+            MI_HIP_CHECK(hipMemcpyAsync(lane_v(LV_D, c), ALPHA + (c0 + c) * lda, sizeof(T) * (size_t) m, hipMemcpyHostToDevice, stream));
+        int first = 0;
+        if (kc.tiles > 0 && !kc.valid) {  // an unfilled tile cache: the first vector fills it, on the single path
+            MI_HIP_CHECK(hipMemsetAsync(sc.get(), 0, sizeof(cg_scalars<T>), stream));
+            kp_raw(lane_v(LV_D, 0), nullptr);
+            launch_train_values_fin<T>(raw.get(), q.get(), ALPHA[c0 * lda + m], (T) bias[c0], m, lane_v(LV_R, 0), stream);
+            first = 1;
+        }
+        if (nvec > first) tiles_multi(LV_D, first, nvec - first, false);
+        for (int c = first; c < nvec; ++c) {
+            const cg_lane L = pool_lane(c);
+            kp_slab_reduce(L, nullptr);
+            launch_train_values_fin<T>(L.raw, q.get(), ALPHA[(c0 + c) * lda + m], (T) bias[c0 + c], m, lane_v(LV_R, c), stream);
+        }
+        for (int c = 0; c < nvec; ++c)
+            MI_HIP_CHECK(hipMemcpyAsync(OUT + (c0 + c) * ldo, lane_v(LV_R, c), sizeof(T) * (size_t) m, hipMemcpyDeviceToHost, stream));
+        MI_HIP_CHECK(hipStreamSynchronize(stream));
+    }
 }
 
 // time_kp's K·p time for the batched product of nrhs resident vectors (groups of at most the width; one at a time

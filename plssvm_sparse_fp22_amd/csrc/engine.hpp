@@ -259,9 +259,11 @@ struct engine : engine_base {
     // (pool_lane). The single solve and a batched group are the same step functions on different views.
     struct cg_lane {
         // the lane's diagonal: 1/C, the QA_cost that goes with it (the centred one where ctr_active()), and the rows'
-        // 1/s_i (null: no point weights) — what kp_fin, cg_fin_dad and cg_product hand to the finalize kernels
+        // 1/s_i (null: no point weights) — what kp_fin, cg_fin_dad and cg_product hand to the finalize kernels; hold: the
+        // lane's held-row flags (null: none; learn_held), read by kp_fin, cg_fin_dad and the lane's init
         T cost_inv, QA;
         const T *sinv;
+        const uint8_t *hold;
         T *x, *r, *d, *Ad, *b, *raw;
         T *cgp;   // 6 RED_BLOCKS: sum d / sum q d, then d.Ad, then r.r
         T *red;   // 2 RED_BLOCKS: the K·p sums and delta0
@@ -273,12 +275,12 @@ struct engine : engine_base {
         T *prr() const { return cgp + 4 * RED_BLOCKS; }
     };
     cg_lane own_lane() const {
-        return { cost_inv(), QAf(), sinv_dev(), x.get(), r.get(), dv.get(), Ad.get(), b.get(), raw.get(), cgp.get(),
+        return { cost_inv(), QAf(), sinv_dev(), hold_cur, x.get(), r.get(), dv.get(), Ad.get(), b.get(), raw.get(), cgp.get(),
                  red.get(), partial.get(), sc.get(), trace.get(), trace_cap };
     }
     cg_lane pool_lane(int c) const {
         const lane_diag &dg = lanes.diag[(size_t) c];
-        return { dg.cost_inv, dg.QA, dg.sinv, lane_v(LV_X, c), lane_v(LV_R, c), lane_v(LV_D, c), lane_v(LV_AD, c),
+        return { dg.cost_inv, dg.QA, dg.sinv, dg.hold, lane_v(LV_X, c), lane_v(LV_R, c), lane_v(LV_D, c), lane_v(LV_AD, c),
                  lane_v(LV_B, c), lane_v(LV_RAW, c), lane_cgp(c), lane_red(c),
                  lanes.slab.get() + (int64_t) c * lanes.sstride, lanes.sc.get() + c,
                  lanes.trace.get() + (int64_t) c * lanes.trace_cap, lanes.trace_cap };
@@ -333,6 +335,7 @@ struct engine : engine_base {
     struct lane_diag {
         T cost_inv, QA;
         const T *sinv;
+        const uint8_t *hold;
     };
     struct lane_pool {
         // every lane's diagonal (cg_lane), set by the batched entry points before they run a group: the engine's own
@@ -340,6 +343,8 @@ struct engine : engine_base {
         std::vector<lane_diag> diag;
         dev_buf<T> sinv;                   // [width][vstride] per-lane 1/s_i: allocated by the first call that passes
                                            // per-lane weights (need_lane_sinv), never for lanes that differ in C only
+        dev_buf<uint8_t> hold;             // [width][vstride] per-lane held-row flags: allocated by the first learn_held
+                                           // call that passes them (need_lane_hold)
         int width = 0;                     // lanes allocated: 0 = not yet, 1 = none fit (one at a time)
         int64_t vstride = 0, sstride = 0;  // elements between two lanes' vectors / slabs
         dev_buf<T> vec;                    // [LV_COUNT][width][vstride], zero padded like the engine's vectors
@@ -349,7 +354,7 @@ struct engine : engine_base {
         dev_buf<double> trace;             // [width][trace_cap]
         int64_t trace_cap = 0;
         int64_t bytes() const {
-            return vec.bytes() + slab.bytes() + part.bytes() + sc.bytes() + trace.bytes() + sinv.bytes();
+            return vec.bytes() + slab.bytes() + part.bytes() + sc.bytes() + trace.bytes() + sinv.bytes() + hold.bytes();
         }
     };
     enum lane_vec { LV_X = 0, LV_R, LV_D, LV_AD, LV_B, LV_RAW, LV_COUNT };
@@ -359,12 +364,16 @@ struct engine : engine_base {
     T *lane_cgp(int c) const { return lanes.part.get() + (int64_t) c * 8 * RED_BLOCKS; }
     T *lane_red(int c) const { return lane_cgp(c) + 6 * RED_BLOCKS; }
     bool multi_batched() const;           // this setup runs the batched path (given memory for two lanes)
-    int64_t lane_bytes(bool with_sinv = false) const;  // device memory of one lane (with_sinv: and its weight vector)
+    // device memory of one lane (with_sinv: and its weight vector; with_hold: and its held-row flags)
+    int64_t lane_bytes(bool with_sinv = false, bool with_hold = false) const;
     // the width the next multi call would use (1: one at a time); allocates nothing
-    int multi_width_next(bool with_sinv = false) const;
-    int multi_lanes(bool with_sinv = false);  // the lanes, allocated at the first call (width halved until it fits)
+    int multi_width_next(bool with_sinv = false, bool with_hold = false) const;
+    // the lanes, allocated at the first call (width halved until it fits)
+    int multi_lanes(bool with_sinv = false, bool with_hold = false);
     bool need_lane_sinv();                // the per-lane weight vectors of an allocated pool; false: no room for them
     T *lane_sinv(int c) const { return lanes.sinv.get() + (int64_t) c * lanes.vstride; }
+    bool need_lane_hold();                // the same for the held-row flags
+    uint8_t *lane_hold(int c) const { return lanes.hold.get() + (int64_t) c * lanes.vstride; }
     void lanes_own_diag();                // every lane: the engine's own cost, QA_cost and weights
     void need_pool();                     // the steps' group / shard / centring handling is the identity here
     void tiles_multi(int kind, int c0, int nvec, bool flags);  // one pass over the tiles for lanes [c0, c0 + nvec)
@@ -373,7 +382,10 @@ struct engine : engine_base {
     // residual); flags: the lanes' stop flags apply
     void kp_lanes(int kin, int kout, int c0, int nvec, T add, bool overwrite, bool flags, bool then_rr = false);
     void cg_iter_multi(int nvec, int reset);
-    void solve_cg_group(const T *B, int nvec, int64_t ld, int64_t imax, T eps, T *X_out, double *trace_out, int64_t *iters);
+    // held: the lanes' diag carries hold rows — x0 is the lane's own (1 on its active rows), so the first residual goes
+    // through kp_lanes per lane instead of the shared first product
+    void solve_cg_group(const T *B, int nvec, int64_t ld, int64_t imax, T eps, T *X_out, double *trace_out, int64_t *iters,
+                        bool held = false);
     void solve_cg_multi(const T *B, int64_t nrhs, int64_t ld, const T *q_host, int64_t imax, T eps, T *X_out,
                         double *trace_out, int64_t *iters);
     void kp_multi(const T *q_host, const T *P, T *RET, int64_t nrhs, int64_t ld, T add);
@@ -382,8 +394,32 @@ struct engine : engine_base {
     // lane k = learn on labels Y[k] with cost costs[k] (null: the engine's) and point weights S[k] (null: the engine's;
     // lds == 0: S is one row for all lanes): batched where multi_batched(), else one after another with the engine's
     // cost and weights set per lane; both are as before on return (also when it throws)
+    // the common argument checks of learn_lanes / learn_held (ERR_ARG), returning the lanes' costs in T; 1 / s of a row
+    std::vector<T> check_lane_args(const T *Y, int64_t nlane, int64_t ldy, const double *costs, const T *S, int64_t lds) const;
+    std::vector<T> recip_weights(const T *s) const;
     void learn_lanes(const T *Y, int64_t nlane, int64_t ldy, const double *costs, const T *S, int64_t lds, int64_t imax,
                      T eps, T *alpha_out, double *bias_out, double *trace_out, int64_t *iters);
+    // ---- held-out points as masked lanes (plssvm_mi_learn_held) ----
+    // learn_lanes whose lane k also leaves out the points with HOLD[k * ldh + i] != 0 (ldh == 0: one row for all lanes;
+    // HOLD null: learn_lanes). The lane's pivot t = its largest training index takes the last point's part: q = column t
+    // of the kernel matrix (t < m: one K·e_t over the tiles, shared by the lanes of that pivot), QA = k_tt + diag_t,
+    // b = y - y_t; the rows i with hold_i or i >= t are masked (lane_diag::hold / hold_cur). Lanes are grouped by pivot,
+    // pivot m first, and returned in the caller's order; pivots_out (nullable) gets t per lane. Batched where the lanes
+    // are, else one after another on own_lane() with hold_cur — the same steps, the same bits. Offered where
+    // held_supported(); the engine's cost, weights and q are as before on return (also when it throws).
+    const uint8_t *hold_cur = nullptr;  // own_lane()'s held-row flags (set by learn_held around a single solve)
+    dev_buf<uint8_t> hold_own;
+    bool held_supported() const;
+    void learn_held(const T *Y, int64_t nlane, int64_t ldy, const double *costs, const T *S, int64_t lds,
+                    const uint8_t *HOLD, int64_t ldh, int64_t imax, T eps, T *alpha_out, double *bias_out,
+                    double *trace_out, int64_t *iters, int64_t *pivots_out);
+    // OUT[c][i] = sum_j k(x_i, x_j) ALPHA[c][j] + bias[c] for every point i < n of the setup (the model's decision values
+    // on its own training points, held-out ones included): one pass over the tiles per group of up to the width
+    // vectors where multi_batched(), else one vector after another through kp_part's code; then train_values_fin. The
+    // last point's sum is a host fma chain in index order. Row c is bitwise the same whatever nclass, position or width.
+    // One GPU: a simulated rank or a group is ERR_UNSUPPORTED. A q that is not the generated one is generated anew (a
+    // caller's q is replaced, QA_cost is kept).
+    void train_values(const T *ALPHA, int64_t nclass, int64_t lda, const double *bias, T *OUT, int64_t ldo);
     void time_kp_multi(int64_t nrhs, int reps, double *ms_kp);
 
     // sparse paths (sparse.hip)

@@ -47,6 +47,33 @@ template <typename T>
 __host__ __device__ __forceinline__ T diag_at(const row_diag<T> &dg, int64_t i) {
     return dg.cost_inv * dg.sinv[i];
 }
+// Held rows (k-fold cross-validation): a lane that trains on a subset solves the principal submatrix
+// of Q~ on its active rows. hold[i] != 0 removes row i: the finalize kernels store T(0) there (also where they add to
+// what is stored) and the row adds nothing to the d.Ad partials; with the vectors zero off the active rows the columns
+// are gone as well. An active row runs the row_diag arithmetic (sinv null: the scalar's), so its bits are those of the
+// other two instances.
+template <typename T>
+struct row_diag_held {
+    T cost_inv;
+    const T *sinv;        // nullable
+    const uint8_t *hold;  // the kernel's own row range (offset like q)
+};
+template <typename T>
+__host__ __device__ __forceinline__ T diag_at(const row_diag_held<T> &dg, int64_t i) {
+    return dg.sinv != nullptr ? dg.cost_inv * dg.sinv[i] : dg.cost_inv;
+}
+template <typename T>
+__host__ __device__ __forceinline__ bool held_at(T, int64_t) {
+    return false;
+}
+template <typename T>
+__host__ __device__ __forceinline__ bool held_at(const row_diag<T> &, int64_t) {
+    return false;
+}
+template <typename T>
+__host__ __device__ __forceinline__ bool held_at(const row_diag_held<T> &dg, int64_t i) {
+    return dg.hold[i] != 0;
+}
 
 // ---- dense pairwise tiles -----------------------------------------------------------------------
 // tile edge of the implicit Q~ tiles (rows and columns); n_pad is a multiple of this.
@@ -164,10 +191,11 @@ void launch_kp_reduce(const T *partial, int64_t nb, int64_t m, int64_t s0, int64
 // ret[i] = (overwrite ? 0 : ret[i]) + add * (raw[i] + (QA - q_i) * sum(p) - sum(q p) + p_i / C)
 // raw may alias ret only when overwrite is false and ... (never aliased by callers).
 // sinv non-null (point weights): the row_diag instance, p_i / C becomes ((1/C) sinv_i) p_i
+// hold non-null (held rows): the row_diag_held instance, ret[i] = T(0) where hold[i] != 0 (overwrite or not)
 template <typename T>
 void launch_kp_finalize(const T *raw, const T *q, const T *p, const cg_scalars<T> *sc, T QA_cost, T cost_inv,
-                        const T *sinv, T add, int overwrite, int64_t m, T *ret, const cg_scalars<T> *status,
-                        hipStream_t s);
+                        const T *sinv, const uint8_t *hold, T add, int overwrite, int64_t m, T *ret,
+                        const cg_scalars<T> *status, hipStream_t s);
 
 // ---- linear factored path: Q~p = X_m (X_m^T p) + rank-1 terms --------------------------------------
 template <typename T>
@@ -191,6 +219,15 @@ void launch_dot_final(const T *partials, cg_scalars<T> *sc, int op, int64_t run,
                       T *plain_out, hipStream_t s, int G = 1);
 template <typename T>
 void launch_cg_init(const T *b, int64_t m, T *x, T *r, hipStream_t s);
+// the same with held rows: x = 1 where hold[i] == 0 and 0 elsewhere; r = b (the caller's b is 0 on held rows)
+template <typename T>
+void launch_cg_init_held(const T *b, const uint8_t *hold, int64_t m, T *x, T *r, hipStream_t s);
+// Decision values of the training points from raw_i = sum_{j < m} k_ij alpha_j (the K·p's raw part):
+// out_i = raw_i + q_i alpha_m + bias for i < m, q_i = k(x_i, x_m). The last point's value, sum_j q_j alpha_j +
+// k_mm alpha_m + bias, is the caller's: engine::train_values sums it on the host as an fma chain in index order, like
+// learn_tail's q . alpha.
+template <typename T>
+void launch_train_values_fin(const T *raw, const T *q, T alpha_m, T bias, int64_t m, T *out, hipStream_t s);
 template <typename T>
 void launch_copy(const T *src, int64_t n, T *dst, const cg_scalars<T> *status, hipStream_t s);
 // x += alpha d; if !reset: r -= alpha Ad  else r = b
@@ -210,8 +247,9 @@ void launch_cg_direction(T *d, const T *r, int64_t m, const cg_scalars<T> *sc, h
 // d.Ad partials -> pdad. slabs != null: raw = the P panel slabs [P][sstride] of an unreduced SpMV pass.
 template <typename T>
 void launch_cg_fin_dad(const T *raw, const T *slabs, int64_t P, int64_t sstride, const T *q, const T *d, const T *psum,
-                       int G, T QA_cost, T cost_inv, const T *sinv, int raw_only, int64_t m, T *Ad, T *pdad,
-                       cg_scalars<T> *sc, hipStream_t s);  // sinv non-null: the row_diag instance
+                       int G, T QA_cost, T cost_inv, const T *sinv, const uint8_t *hold, int raw_only, int64_t m, T *Ad,
+                       T *pdad, cg_scalars<T> *sc, hipStream_t s);  // sinv non-null: the row_diag instance; hold non-null:
+                                                                    // row_diag_held, Ad = 0 and no d.Ad term on held rows
 // alpha = delta / d.Ad (pdad); x += alpha d; r -= alpha Ad and r.r partials -> prr (reset: r = b)
 template <typename T>
 void launch_cg_upd_rr(T *x, T *r, const T *d, const T *Ad, const T *b, int reset, const T *pdad, int G, int64_t m,

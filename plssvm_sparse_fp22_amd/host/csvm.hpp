@@ -11,7 +11,9 @@
 #include <algorithm>
 #include <charconv>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
+#include <map>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -245,6 +247,68 @@ class csvm : public csvm_interface<T> {
         costs_ = costs;
     }
     const std::vector<T> &costs() const { return costs_; }
+
+    // k-fold cross-validation of the binary problem at every cost of `costs` (build-defined; LIBSVM's -v): the
+    // nfold x costs.size() subset problems as lanes of one plssvm_mi_learn_held call over the setup's stored kernel
+    // matrix, plssvm_mi_train_values, then every point's value from the model that did not see it. Returns the
+    // accuracy per cost; held_values() / folds() keep the values [costs][n] and the fold of every point. One device;
+    // the class weights apply as in learn_costs; no model is set.
+    // stratified_folds: fold of point i = (its rank among the points of its label, in index order) mod nfold
+    static std::vector<int64_t> stratified_folds(const std::vector<T> &labels, std::size_t nfold) {
+        if (nfold < 2 || nfold > labels.size())
+            throw exception{ "The number of folds (" + std::to_string(nfold) + ") must be between 2 and the number of data points (" +
+                             std::to_string(labels.size()) + ")!" };
+        std::map<T, int64_t> seen;
+        std::vector<int64_t> folds(labels.size());
+        for (size_t i = 0; i < labels.size(); ++i) folds[i] = seen[labels[i]]++ % (int64_t) nfold;
+        return folds;
+    }
+    std::vector<double> cross_validate(std::size_t nfold, const std::vector<T> &costs) { return cross_validate(nfold, costs, this->num_features_); }
+    std::vector<double> cross_validate(std::size_t nfold, const std::vector<T> &costs_in, std::size_t imax) {
+        if (this->value_ptr_ == nullptr) throw exception{ "No labels given for training! Maybe the data is only usable for prediction?" };
+        if (grp_->size() != 1) throw exception{ "Cross-validation runs on one device!" };
+        const std::vector<T> costs = costs_in.empty() ? std::vector<T>{ this->cost_ } : costs_in;
+        for (const T c : costs)
+            if (!(c > T(0)) || !std::isfinite(c)) throw exception{ "cross_validate: every cost must be a finite number > 0!" };
+        const std::vector<T> &y = *this->value_ptr_;
+        const size_t n = this->num_data_points_, C = costs.size(), K = C * nfold;
+        folds_ = stratified_folds(y, nfold);
+        const std::vector<T> s = this->point_weights();
+        std::vector<T> Y(K * n), al(K * n), out(K * n);
+        std::vector<uint8_t> H(K * n);
+        std::vector<double> cd(K), bi(K);
+        std::vector<int64_t> its(K), piv(K);
+        for (size_t k = 0; k < K; ++k) {  // lane = cost * nfold + fold
+            std::copy(y.begin(), y.end(), Y.begin() + k * n);
+            cd[k] = (double) costs[k / nfold];
+            for (size_t i = 0; i < n; ++i) H[k * n + i] = folds_[i] == (int64_t) (k % nfold) ? 1 : 0;
+        }
+        if (!on_device_) setup_data_on_device();
+        apply_point_weights(s);
+        on_all([&](int, plssvm_mi_ctx *c) {
+            const int rc = plssvm_mi_learn_held(c, Y.data(), (int64_t) K, (int64_t) n, cd.data(), nullptr, 0, H.data(), (int64_t) n,
+                                                (int64_t) imax, (double) this->epsilon_, al.data(), bi.data(), nullptr, its.data(),
+                                                piv.data());
+            if (rc != PLSSVM_MI_OK) return rc;
+            return plssvm_mi_train_values(c, al.data(), (int64_t) K, (int64_t) n, bi.data(), out.data(), (int64_t) n);
+        });
+        held_values_.assign(C * n, T(0));
+        std::vector<double> acc(C);
+        for (size_t c = 0; c < C; ++c) {
+            size_t ok = 0;
+            for (size_t i = 0; i < n; ++i) {
+                const T v = out[(c * nfold + (size_t) folds_[i]) * n + i];
+                held_values_[c * n + i] = v;
+                ok += (v > T(0) ? T(1) : T(-1)) == (y[i] > T(0) ? T(1) : T(-1));
+            }
+            acc[c] = (double) ok / (double) n;
+        }
+        cv_iterations_ = std::move(its);
+        return acc;
+    }
+    const std::vector<T> &held_values() const { return held_values_; }  // [costs][n], row-major
+    const std::vector<int64_t> &folds() const { return folds_; }
+    const std::vector<int64_t> &cv_iterations() const { return cv_iterations_; }  // [costs][nfold]
 
   private:
     // plssvm_mi_learn_lanes on every rank; the results of rank 0 into alphas_, biases_, iterations_multi_, traces_
@@ -489,6 +553,8 @@ class csvm : public csvm_interface<T> {
     bool on_device_ = false;
     // the one-vs-all model (learn_multi / set_model_multi)
     std::vector<T> classes_, alphas_, biases_, costs_;  // costs_: learn_costs' grid (then classes_ is empty)
+    std::vector<T> held_values_;  // cross_validate
+    std::vector<int64_t> folds_, cv_iterations_;
     std::vector<int64_t> iterations_multi_;
     std::vector<std::vector<double>> traces_;
 };

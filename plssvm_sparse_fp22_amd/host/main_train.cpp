@@ -6,7 +6,9 @@
 // --max_iter overrides the CG limit (default: num_features, csvm.cpp:256), --single trains in fp32
 // (the reference selects that at compile time, main_train.cpp:21-25), --device picks the GPU, --multiclass trains
 // one-vs-all over the file's distinct labels (three or more) and writes the one-vs-all model file, --class_weights
-// L1:W1,L2:W2 trains the points of label Li at cost C * Wi (LIBSVM's -wi; with --multiclass: the positives of class Li).
+// L1:W1,L2:W2 trains the points of label Li at cost C * Wi (LIBSVM's -wi; with --multiclass: the positives of class Li),
+// -v n runs n-fold cross-validation instead of training (LIBSVM's -v: no model file; stratified folds without random
+// numbers, csvm<T>::stratified_folds) and --cv_costs c1,c2,... does so at every listed cost in the same pass.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -49,7 +51,9 @@ const char *kHelp =
     "                             in-process host exchange instead of RCCL)\n"
     "      --multiclass           one-vs-all over the file's distinct labels (three or more classes)\n"
     "      --class_weights arg    L1:W1,L2:W2,...: train the points of label Li at cost C * Wi, all others at C\n"
-    "                             (with --multiclass: the points of class Li in class Li's own problem)\n";
+    "                             (with --multiclass: the points of class Li in class Li's own problem)\n"
+    "  -v, --cross_validation arg n-fold cross validation mode: prints the accuracy, writes no model (one device)\n"
+    "      --cv_costs arg         c1,c2,...: with -v, the accuracy at each of these costs and the best one\n";
 
 // "L1:W1,L2:W2" -> {label: weight}; false (with the reason in why) for a malformed list or a weight that is not > 0
 template <typename T>
@@ -118,6 +122,46 @@ int train(const cli &c) {
         std::fprintf(stderr, "The laplacian kernel takes dense input: it cannot be combined with --sparse!\n");
         return EXIT_FAILURE;
     }
+    // cross-validation: what the options alone decide, before the file is read or a GPU touched
+    const bool cv = c.opt.count("cross_validation") > 0;
+    long long nfold = 0;
+    std::vector<T> cv_costs;
+    if (c.opt.count("cv_costs") && !cv) {
+        std::fprintf(stderr, "--cv_costs needs -v (the number of folds)!\n");
+        return EXIT_FAILURE;
+    }
+    if (cv) {
+        char *end = nullptr;
+        const std::string &vs = c.opt.at("cross_validation");
+        nfold = std::strtoll(vs.c_str(), &end, 10);
+        if (vs.empty() || *end != '\0' || nfold < 2) {
+            std::fprintf(stderr, "-v: n-fold cross validation needs n >= 2, not '%s'!\n", vs.c_str());
+            return EXIT_FAILURE;
+        }
+        if (c.opt.count("multiclass")) {
+            std::fprintf(stderr, "-v cross-validates the binary problem: it cannot be combined with --multiclass!\n");
+            return EXIT_FAILURE;
+        }
+        if (c.opt.count("devices") && c.opt.at("devices").find(',') != std::string::npos) {
+            std::fprintf(stderr, "-v runs on one device: --devices lists more than one!\n");
+            return EXIT_FAILURE;
+        }
+        if (c.opt.count("cv_costs")) {
+            const std::string &l = c.opt.at("cv_costs");
+            for (size_t a = 0; a <= l.size();) {
+                const size_t b = std::min(l.find(',', a), l.size());
+                const std::string item = l.substr(a, b - a);
+                char *e = nullptr;
+                const double v = std::strtod(item.c_str(), &e);
+                if (item.empty() || *e != '\0' || !(v > 0) || !std::isfinite(v) || !((T) v > T(0)) || !std::isfinite((T) v)) {
+                    std::fprintf(stderr, "--cv_costs: '%s' is not a finite number > 0!\n", item.c_str());
+                    return EXIT_FAILURE;
+                }
+                cv_costs.push_back((T) v);
+                a = b + 1;
+            }
+        }
+    }
     std::map<T, T> weights;
     if (c.opt.count("class_weights")) {  // syntax and signs: before the file is read or a GPU touched
         std::string why;
@@ -137,6 +181,11 @@ int train(const cli &c) {
             return EXIT_FAILURE;
         }
     if (c.pos.size() > 1) params.model_filename = c.pos[1];
+    if (cv && nfold > (long long) params.num_data_points) {
+        std::fprintf(stderr, "-v: %lld folds are more than the %lld data points of '%s'!\n", nfold, (long long) params.num_data_points,
+                     c.pos[0].c_str());
+        return EXIT_FAILURE;
+    }
     if (multiclass) {
         std::vector<T> distinct = params.class_labels;
         std::sort(distinct.begin(), distinct.end());
@@ -179,6 +228,8 @@ int train(const cli &c) {
         }
     } else if (c.opt.count("device")) {
         devs.push_back(std::stoi(c.opt.at("device")));
+    } else if (cv) {
+        devs.push_back(0);
     } else {
         devs = csvm<T>::all_devices(params);
     }
@@ -188,6 +239,23 @@ int train(const cli &c) {
         std::printf("Found %d HIP device(s):\n", svm.num_devices());
         for (const int d : svm.devices()) std::printf("  [%d, gfx950]\n", d);
         std::printf("\n");
+    }
+    if (cv) {
+        // LIBSVM's -v: the accuracy on the held-out folds, no model file
+        const std::size_t imax = c.opt.count("max_iter") ? (std::size_t) std::stoll(c.opt.at("max_iter")) : (std::size_t) params.num_features;
+        const std::vector<double> acc = svm.cross_validate((std::size_t) nfold, cv_costs, imax);
+        if (cv_costs.empty()) {
+            std::printf("Cross Validation Accuracy = %g%%\n", 100 * acc[0]);
+        } else {
+            size_t best = 0;
+            for (size_t k = 0; k < acc.size(); ++k) {
+                std::printf("C = %s: Cross Validation Accuracy = %g%%\n", csvm<T>::shortest(cv_costs[k]).c_str(), 100 * acc[k]);
+                // a tie goes to the smaller cost
+                if (acc[k] > acc[best] || (acc[k] == acc[best] && cv_costs[k] < cv_costs[best])) best = k;
+            }
+            std::printf("Best C = %s (Cross Validation Accuracy = %g%%)\n", csvm<T>::shortest(cv_costs[best]).c_str(), 100 * acc[best]);
+        }
+        return EXIT_SUCCESS;
     }
     // learn() prints the reference's setup line, one line per CG iteration and the solve summary
     // (csvm.cpp:226-266, OpenMP/csvm.cpp:115-117,161-166)
@@ -220,7 +288,8 @@ int main(int argc, char **argv) {
     try {
         const cli c = parse_cli(argc, argv, { { "t", "kernel_type" }, { "d", "degree" }, { "g", "gamma" }, { "r", "coef0" },
                                               { "c", "cost" }, { "e", "epsilon" }, { "b", "backend" },
-                                              { "p", "target_platform" }, { "q", "quiet" }, { "h", "help" } },
+                                              { "p", "target_platform" }, { "q", "quiet" }, { "h", "help" },
+                                              { "v", "cross_validation" } },
                                 { "quiet", "help", "sparse", "single", "multiclass" });
         if (c.opt.count("help")) {
             std::printf("%s", kHelp);
