@@ -342,7 +342,8 @@ PLSSVM_MI_API int plssvm_mi_learn_lanes(plssvm_mi_ctx *ctx, const void *Y, int64
  *     with the pairwise tile kernels, on one GPU, with the reference CG. A stored sparse setup, the factored linear
  *     path, a group, a simulated rank or the one-reduction CG with a non-NULL HOLD: PLSSVM_MI_ERR_UNSUPPORTED,
  *     plssvm_mi_last_error names the setup, the context stays usable.
- * Other arguments and outputs as plssvm_mi_learn_lanes'. 0 < ldh < n, or a lane with fewer than two training points:
+ * Other arguments and outputs as plssvm_mi_learn_lanes': row k of delta_trace is filled up to iters[k], as
+ * plssvm_mi_solve_cg_multi fills it, and not written beyond. 0 < ldh < n, or a lane with fewer than two training points:
  * PLSSVM_MI_ERR_ARG. The context's cost, weights and q are what they were when the call returns. */
 PLSSVM_MI_API int plssvm_mi_learn_held(plssvm_mi_ctx *ctx, const void *Y, int64_t nlane, int64_t ldy, const double *costs,
                                        const void *S, int64_t lds, const uint8_t *HOLD, int64_t ldh, int64_t imax,

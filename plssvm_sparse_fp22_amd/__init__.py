@@ -507,8 +507,9 @@ class CSVM:
         self.traces = [trace[c, : it[c] + 1].copy() for c in range(R)]
         return X[:, : self.m]
 
-    def _learn_lanes(self, Y, costs, S, imax):
-        """plssvm_mi_learn_lanes on Y [K][n]: costs [K] or None, S [K][n] / [n] (one row for all) or None."""
+    def _learn_lanes(self, Y, costs, S, imax, hold=None):
+        """plssvm_mi_learn_lanes on Y [K][n]: costs [K] or None, S [K][n] / [n] (one row for all) or None; with hold
+        (uint8 [K][n]) plssvm_mi_learn_held, which also sets pivots."""
         K, n = Y.shape
         im = self.num_features if imax < 0 else imax
         alphas = np.zeros((K, n), dtype=self.dtype)
@@ -522,9 +523,14 @@ class CSVM:
         if SS is not None and SS.shape not in ((K, n), (n,)):
             raise ValueError(f"the weights must be [{K}][{n}] or one row of {n}")
         lds = 0 if SS is None or SS.ndim == 1 else SS.shape[1]
-        self._check(_abi.lib().plssvm_mi_learn_lanes(self._ctx, _ptr(Y), K, n, _ptr(cc), _ptr(SS), lds, im,
-                                                     float(self.params.epsilon), _ptr(alphas), _ptr(biases),
-                                                     _ptr(trace), _ptr(it)))
+        out = (im, float(self.params.epsilon), _ptr(alphas), _ptr(biases), _ptr(trace), _ptr(it))
+        if hold is None:
+            self._check(_abi.lib().plssvm_mi_learn_lanes(self._ctx, _ptr(Y), K, n, _ptr(cc), _ptr(SS), lds, *out))
+        else:
+            piv = np.zeros(K, dtype=np.int64)
+            self._check(_abi.lib().plssvm_mi_learn_held(self._ctx, _ptr(Y), K, n, _ptr(cc), _ptr(SS), lds, _ptr(hold), n,
+                                                        *out, _ptr(piv)))
+            self.pivots = piv
         self.alphas = alphas
         self.biases = biases.astype(self.dtype)
         self.iters_multi = it
@@ -568,29 +574,7 @@ class CSVM:
             self.setup_data_on_device()
         self._apply_class_weight(cw)
         y = np.ascontiguousarray(self.params.labels, dtype=self.dtype)
-        Y = np.ascontiguousarray(np.tile(y, (K, 1)))
-        im = self.num_features if imax < 0 else imax
-        alphas = np.zeros((K, n), dtype=self.dtype)
-        biases = np.zeros(K, dtype=np.float64)
-        trace = np.full((K, im + 1), np.nan)
-        it = np.zeros(K, dtype=np.int64)
-        piv = np.zeros(K, dtype=np.int64)
-        cc = None if costs is None else np.ascontiguousarray(costs, dtype=np.float64)
-        SS = None if S is None else np.ascontiguousarray(S, dtype=self.dtype)
-        if cc is not None and cc.shape != (K,):
-            raise ValueError(f"costs must have {K} entries")
-        if SS is not None and SS.shape not in ((K, n), (n,)):
-            raise ValueError(f"the weights must be [{K}][{n}] or one row of {n}")
-        lds = 0 if SS is None or SS.ndim == 1 else SS.shape[1]
-        self._check(_abi.lib().plssvm_mi_learn_held(self._ctx, _ptr(Y), K, n, _ptr(cc), _ptr(SS), lds, _ptr(H), n, im,
-                                                    float(self.params.epsilon), _ptr(alphas), _ptr(biases), _ptr(trace),
-                                                    _ptr(it), _ptr(piv)))
-        self.alphas = alphas
-        self.biases = biases.astype(self.dtype)
-        self.iters_multi = it
-        self.traces = [trace[c, : it[c] + 1].copy() for c in range(K)]
-        self.pivots = piv
-        return self
+        return self._learn_lanes(np.ascontiguousarray(np.tile(y, (K, 1))), costs, S, imax, hold=H)
 
     def train_values(self, alphas=None, biases=None):
         """Decision values [n][K] of K models (default: alphas, biases as the last multi-lane learn left them) on the
@@ -673,23 +657,8 @@ class CSVM:
         if not self._on_device:
             self.setup_data_on_device()
         self._apply_class_weight(None)  # the binary class_weight of an earlier learn() does not reach the classes
-        if S is not None:
-            self._learn_lanes(Y, None, S, imax)
-            self.classes = classes
-            return self
-        K, n = Y.shape
-        im = self.num_features if imax < 0 else imax
-        alphas = np.zeros((K, n), dtype=self.dtype)
-        biases = np.zeros(K, dtype=np.float64)
-        trace = np.full((K, im + 1), np.nan)
-        it = np.zeros(K, dtype=np.int64)
-        self._check(_abi.lib().plssvm_mi_learn_multi(self._ctx, _ptr(Y), K, n, im, float(self.params.epsilon),
-                                                     _ptr(alphas), _ptr(biases), _ptr(trace), _ptr(it)))
+        self._learn_lanes(Y, None, S, imax)  # S None: plssvm_mi_learn_multi's call, lanes that differ in b only
         self.classes = classes
-        self.alphas = alphas
-        self.biases = biases.astype(self.dtype)
-        self.iters_multi = it
-        self.traces = [trace[c, : it[c] + 1].copy() for c in range(K)]
         return self
 
     def predict_values_multi(self, points, val_fmt=None, alphas=None, biases=None):

@@ -15,14 +15,9 @@
 #include <stdexcept>
 #include <string>
 
-namespace plssvm_mi {
+#include "mi_error.hpp"
 
-// Error carrier turned into a PLSSVM_MI_ERR_* code at the C ABI (the reference throws
-// plssvm::hip::backend_exception from PLSSVM_HIP_ERROR_CHECK, src/plssvm/backends/HIP/detail/utility.hip.cpp:19-23).
-struct mi_error : std::runtime_error {
-    int code;
-    mi_error(int c, const std::string &msg) : std::runtime_error(msg), code(c) {}
-};
+namespace plssvm_mi {
 
 // the PLSSVM_MI_ERR_* code of any exception a setup step may raise (mi_error: its code; host or device
 // allocation: ERR_OOM; anything else, e.g. std::length_error from a host table: ERR_ARG — the C ABI's mapping)

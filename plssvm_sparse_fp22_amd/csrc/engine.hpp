@@ -211,6 +211,7 @@ struct engine : engine_base {
     bool ctr_active() const;
     const T *qf() const { return ctr_active() ? ctr_h.get() : q.get(); }
     T QAf() const;
+    T k_mm() const;  // k(x_m, x_m) on the host, as generate_q's QA_cost has it
     void ctr_setup();
     cg_scalars<T> polled{};               // the CG scalars read by the last cg_step poll
     // plssvm_mi_set_progress: called by solve_cg after each polled batch of iterations
@@ -231,7 +232,6 @@ struct engine : engine_base {
     bool weighted() const { return !sinv_h.empty(); }
     const T *sinv_dev() const { return weighted() ? sinv.get() : nullptr; }
     T diag_m() const { return weighted() ? cost_inv() * sinv_h[(size_t) m] : cost_inv(); }  // the last point's diagonal
-    static void check_weights(const T *s, int64_t count);  // finite and > 0, else ERR_ARG
     void set_sinv(const std::vector<T> &sinv_new);          // the reciprocals (n, or empty: none); QA_cost follows
     void set_point_weights(const T *s);                    // s[n], null clears
     bool factored() const;
@@ -252,6 +252,8 @@ struct engine : engine_base {
     // out = (overwrite ? 0 : out) + add * Q~ p  (device vectors, length >= m)
     void kp_device(const T *p, T *out, T add, bool overwrite, const cg_scalars<T> *status);
     void kp_raw(const T *p, const cg_scalars<T> *status);  // raw = the pairwise / sparse part of Q~ p
+    // kp_raw of a host vector (m values) or, p_host null, of the unit vector e_t (t < 0: of zero), through sc and pv
+    void kp_raw_of(const T *p_host, int64_t t = -1, int part = 0);
     void kp_host(const T *q_host, const T *p, T *ret_host, T add);
 
     // ---- one right-hand side's device state, and the steps of K·p and CG on it ----
@@ -306,8 +308,6 @@ struct engine : engine_base {
     static cg_scalars<T> cg_scalars_init(T eps, bool force);
     // iterations until the next host poll: 4, 8, 16, ... up to the first reset, then blocks of CG_RESET
     static int64_t poll_batch(int64_t done, int64_t imax, int64_t &batch);
-    // csvm::learn's end (csvm.cpp:257-258): alpha[m] = -sum alpha, bias = y_m + QA_cost sum alpha - q . alpha
-    void learn_tail(const T *y, const T *q_host, T QA, T *alpha, double *bias_out) const;
 
     void cg_begin(const T *b_host, const T *q_host, T eps, bool force, double *delta0_out, int64_t trace_len);
     void cg_iter(int reset);
@@ -321,9 +321,10 @@ struct engine : engine_base {
     void learn(const T *y, int64_t imax, T eps, T *alpha_out, double *bias_out, double *trace_out, int64_t *iters);
     void time_kp(int reps, double *ms_kp, double *ms_dom);
 
-    // ---- several right-hand sides over one pass of the tiles ----
-    // The one-vs-all systems of a multi-class problem share Q~ and differ in b, so their CG solves run as lanes: a
-    // lane is one right-hand side's device state (x, r, d, Ad, b, raw, its partials, cg_scalars, trace and tile slab).
+    // ---- several right-hand sides over one pass of the tiles (lanes.hip) ----
+    // Systems that share the kernel matrix — one-vs-all classes (they differ in b), a cost grid or weighted classes (in
+    // the diagonal), folds (in the rows they leave out) — run their CG solves as lanes: a lane is one right-hand side's
+    // device state (x, r, d, Ad, b, raw, its partials, cg_scalars, trace and tile slab) and its lane_diag.
     // Each iteration makes ONE pass over the tiles for the live lanes' direction vectors (launch_kp_tiles_multi) and
     // then runs the step functions above on each lane's view (pool_lane) — the very functions cg_begin and cg_iter
     // run on own_lane() — so every lane's x, trace and iteration count are bitwise solve_cg's on that right-hand
@@ -339,12 +340,12 @@ struct engine : engine_base {
     };
     struct lane_pool {
         // every lane's diagonal (cg_lane), set by the batched entry points before they run a group: the engine's own
-        // (lanes_own_diag: the one-vs-all classes) or the lane's cost and weights (learn_lanes)
+        // (lanes_own_diag) or the lane's cost, weights and hold rows (learn_held, from its lane_plan)
         std::vector<lane_diag> diag;
         dev_buf<T> sinv;                   // [width][vstride] per-lane 1/s_i: allocated by the first call that passes
-                                           // per-lane weights (need_lane_sinv), never for lanes that differ in C only
+                                           // per-lane weights (need_lane_buf), never for lanes that differ in C only
         dev_buf<uint8_t> hold;             // [width][vstride] per-lane held-row flags: allocated by the first learn_held
-                                           // call that passes them (need_lane_hold)
+                                           // call that passes them (need_lane_buf)
         int width = 0;                     // lanes allocated: 0 = not yet, 1 = none fit (one at a time)
         int64_t vstride = 0, sstride = 0;  // elements between two lanes' vectors / slabs
         dev_buf<T> vec;                    // [LV_COUNT][width][vstride], zero padded like the engine's vectors
@@ -363,17 +364,30 @@ struct engine : engine_base {
     T *lane_v(int kind, int c) const { return lanes.vec.get() + ((int64_t) kind * lanes.width + c) * lanes.vstride; }
     T *lane_cgp(int c) const { return lanes.part.get() + (int64_t) c * 8 * RED_BLOCKS; }
     T *lane_red(int c) const { return lane_cgp(c) + 6 * RED_BLOCKS; }
-    bool multi_batched() const;           // this setup runs the batched path (given memory for two lanes)
+    // where the lanes' steps are the single solve's (the tile path on one rank with the reference CG): held-out lanes
+    // are offered there; batched there unless multi_opt == 1 (and given memory for two lanes)
+    bool held_supported() const;
+    bool multi_batched() const;
     // device memory of one lane (with_sinv: and its weight vector; with_hold: and its held-row flags)
     int64_t lane_bytes(bool with_sinv = false, bool with_hold = false) const;
     // the width the next multi call would use (1: one at a time); allocates nothing
     int multi_width_next(bool with_sinv = false, bool with_hold = false) const;
     // the lanes, allocated at the first call (width halved until it fits)
     int multi_lanes(bool with_sinv = false, bool with_hold = false);
-    bool need_lane_sinv();                // the per-lane weight vectors of an allocated pool; false: no room for them
+    // a per-lane buffer (lanes.sinv, lanes.hold) of an allocated pool, allocated on first need; false: no room for it
+    template <typename U>
+    bool need_lane_buf(dev_buf<U> &buf);
     T *lane_sinv(int c) const { return lanes.sinv.get() + (int64_t) c * lanes.vstride; }
-    bool need_lane_hold();                // the same for the held-row flags
     uint8_t *lane_hold(int c) const { return lanes.hold.get() + (int64_t) c * lanes.vstride; }
+    // The batched launch streams filled records only: if the tile cache is allocated and unfilled, `product` (a K·p of
+    // the caller's choice on the single path, after sc is zeroed) fills it; true if it ran
+    template <typename F>
+    bool fill_tiles(F product) {
+        if (kc.tiles <= 0 || kc.valid) return false;
+        MI_HIP_CHECK(hipMemsetAsync(sc.get(), 0, sizeof(cg_scalars<T>), stream));
+        product();
+        return true;
+    }
     void lanes_own_diag();                // every lane: the engine's own cost, QA_cost and weights
     void need_pool();                     // the steps' group / shard / centring handling is the identity here
     void tiles_multi(int kind, int c0, int nvec, bool flags);  // one pass over the tiles for lanes [c0, c0 + nvec)
@@ -389,30 +403,35 @@ struct engine : engine_base {
     void solve_cg_multi(const T *B, int64_t nrhs, int64_t ld, const T *q_host, int64_t imax, T eps, T *X_out,
                         double *trace_out, int64_t *iters);
     void kp_multi(const T *q_host, const T *P, T *RET, int64_t nrhs, int64_t ld, T add);
-    void learn_multi(const T *Y, int64_t nclass, int64_t ldy, int64_t imax, T eps, T *alpha_out, double *bias_out,
-                     double *trace_out, int64_t *iters);
-    // lane k = learn on labels Y[k] with cost costs[k] (null: the engine's) and point weights S[k] (null: the engine's;
-    // lds == 0: S is one row for all lanes): batched where multi_batched(), else one after another with the engine's
-    // cost and weights set per lane; both are as before on return (also when it throws)
-    // the common argument checks of learn_lanes / learn_held (ERR_ARG), returning the lanes' costs in T; 1 / s of a row
-    std::vector<T> check_lane_args(const T *Y, int64_t nlane, int64_t ldy, const double *costs, const T *S, int64_t lds) const;
-    std::vector<T> recip_weights(const T *s) const;
-    void learn_lanes(const T *Y, int64_t nlane, int64_t ldy, const double *costs, const T *S, int64_t lds, int64_t imax,
-                     T eps, T *alpha_out, double *bias_out, double *trace_out, int64_t *iters);
-    // ---- held-out points as masked lanes (plssvm_mi_learn_held) ----
-    // learn_lanes whose lane k also leaves out the points with HOLD[k * ldh + i] != 0 (ldh == 0: one row for all lanes;
-    // HOLD null: learn_lanes). The lane's pivot t = its largest training index takes the last point's part: q = column t
-    // of the kernel matrix (t < m: one K·e_t over the tiles, shared by the lanes of that pivot), QA = k_tt + diag_t,
-    // b = y - y_t; the rows i with hold_i or i >= t are masked (lane_diag::hold / hold_cur). Lanes are grouped by pivot,
-    // pivot m first, and returned in the caller's order; pivots_out (nullable) gets t per lane. Batched where the lanes
-    // are, else one after another on own_lane() with hold_cur — the same steps, the same bits. Offered where
-    // held_supported(); the engine's cost, weights and q are as before on return (also when it throws).
+    // ---- the multi-lane learn (plssvm_mi_learn_multi / _learn_lanes / _learn_held) ----
+    // Lane k = learn on the labels Y[k] at cost costs[k] (null: the engine's) with the point weights S[k] (null: the
+    // engine's; lds == 0: S is one row for all lanes), leaving out the points with HOLD[k * ldh + i] != 0 (ldh == 0: one
+    // row for all lanes; HOLD null: no lane is masked, and every setup serves the call). The host half is a lane_plan
+    // (lane_plan.hpp): every argument check, before anything moves; per lane its cost, weight row, hold row and pivot t =
+    // its largest training index (m without hold rows), which takes the last point's part: q = column t of the kernel
+    // matrix (t < m: one K·e_t over the tiles, shared by the lanes of that pivot), QA = k_tt + diag_t, b = y - y_t; the
+    // rows i with hold_i or i >= t are masked (lane_diag::hold / hold_cur). The lanes run grouped by pivot, pivot m first,
+    // and are returned in the caller's order; pivots_out (nullable) gets t per lane. Batched where multi_batched() and
+    // the per-lane buffers fit, else one after another on own_lane() with the engine's cost, weights and hold_cur set per
+    // lane — the same steps, the same bits. Without hold rows the lanes share the first product Q~ x0 and run the
+    // unmasked kernel instances; with them each lane's x0 is its own. Held lanes are offered where held_supported()
+    // (else ERR_UNSUPPORTED, after the argument checks). One restore rule: the call records what it moved of the
+    // engine's cost, QA_cost, weights, q and hold_cur and undoes exactly that on every exit, thrown or not, resetting
+    // the captured CG graph only if a value a captured block holds was moved — learn_multi without weights moves nothing.
     const uint8_t *hold_cur = nullptr;  // own_lane()'s held-row flags (set by learn_held around a single solve)
     dev_buf<uint8_t> hold_own;
-    bool held_supported() const;
     void learn_held(const T *Y, int64_t nlane, int64_t ldy, const double *costs, const T *S, int64_t lds,
                     const uint8_t *HOLD, int64_t ldh, int64_t imax, T eps, T *alpha_out, double *bias_out,
                     double *trace_out, int64_t *iters, int64_t *pivots_out);
+    void learn_lanes(const T *Y, int64_t nlane, int64_t ldy, const double *costs, const T *S, int64_t lds, int64_t imax,
+                     T eps, T *alpha_out, double *bias_out, double *trace_out, int64_t *iters) {
+        learn_held(Y, nlane, ldy, costs, S, lds, nullptr, 0, imax, eps, alpha_out, bias_out, trace_out, iters, nullptr);
+    }
+    // learn() per class of a one-vs-all label matrix Y[nclass][ldy] (+-1): lanes that differ in b only
+    void learn_multi(const T *Y, int64_t nclass, int64_t ldy, int64_t imax, T eps, T *alpha_out, double *bias_out,
+                     double *trace_out, int64_t *iters) {
+        learn_lanes(Y, nclass, ldy, nullptr, nullptr, 0, imax, eps, alpha_out, bias_out, trace_out, iters);
+    }
     // OUT[c][i] = sum_j k(x_i, x_j) ALPHA[c][j] + bias[c] for every point i < n of the setup (the model's decision values
     // on its own training points, held-out ones included): one pass over the tiles per group of up to the width
     // vectors where multi_batched(), else one vector after another through kp_part's code; then train_values_fin. The

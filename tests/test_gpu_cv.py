@@ -486,6 +486,69 @@ def test_bad_arguments_leave_the_context_usable(dtype):
         assert same(solved(svm.learn(IMAX)), before)
 
 
+@pytest.mark.parametrize("multi_width", [None, 1], ids=["auto", "width1"])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_every_lane_call_leaves_the_context_as_found(dtype, multi_width):
+    """One context with point weights and a cost of its own: after every kind of multi-lane call — classes, a cost grid,
+    per-lane weights, held lanes with a moved pivot, held lanes with nothing held, and calls refused with ERR_ARG in their
+    last lane — first solver_CG with q = None, which solves with the q and QA_cost it finds in place, and then learn(),
+    which forms q and QA_cost anew from the cost and the weights, return the bits they returned before: q, QA_cost, the
+    cost, the weights and the hold rows are back. Batched and one lane at a time; the width that ran is asserted."""
+    n, d = 301, 12
+    X, y, g, _ = ref.blobs_case(n, d, dtype, "rbf")
+    rng = np.random.default_rng(301)
+    s = rng.uniform(0.5, 2.0, n).astype(dtype)
+    S2 = rng.uniform(0.5, 2.0, (2, n)).astype(dtype)
+    Y2 = np.ascontiguousarray(np.tile(np.asarray(y, dtype=dtype), (2, 1)))
+    last = np.zeros((2, n), dtype=bool)
+    last[:, n - 1] = True  # the pivot moves to n - 2
+    one_left = np.zeros((2, n), dtype=bool)
+    one_left[1, :] = True
+    one_left[1, 17] = False
+    S_bad = S2.copy()
+    S_bad[1, 5] = 0.0
+    eps = 1e-10 if dtype == np.float64 else 1e-6
+
+    def refused(call):
+        with pytest.raises(pm.BackendError) as e:
+            call()
+        assert e.value.code == ERR_ARG
+
+    with dense_svm("rbf", X, y, g, dtype, epsilon=eps, multi_width=multi_width) as svm:
+        svm.set_point_weights(s)
+        before = solved(svm.learn(IMAX))
+        assert before[2] > 0 and svm.info()["multi_width"] == (8 if multi_width is None else 1)
+        b = (np.asarray(y, dtype=dtype)[: n - 1] - dtype(y[n - 1])).astype(dtype)
+
+        def in_place():  # a solve on the q and QA_cost in place
+            x = svm.solver_CG(b, IMAX, eps)
+            return x.copy(), int(svm.iters), svm.trace.copy()
+
+        found = in_place()
+        assert found[1] > 0
+        calls = {
+            "learn_multi": lambda: svm.learn_multi(np.arange(n) % 3, IMAX),
+            "learn_costs": lambda: svm.learn_costs([0.5, 30.0], IMAX),
+            "per-lane weights": lambda: svm._learn_lanes(Y2, None, S2, IMAX),
+            "held, moved pivot, per-lane weights": lambda: svm.learn_held(last, S=S2, imax=IMAX),
+            "held, nothing held, per-lane weights": lambda: svm.learn_held(np.zeros((2, n), dtype=bool), S=S2, imax=IMAX),
+            "a cost of -1": lambda: refused(lambda: svm._learn_lanes(Y2, np.array([0.5, -1.0]), None, IMAX)),
+            "a weight of 0": lambda: refused(lambda: svm._learn_lanes(Y2, None, S_bad, IMAX)),
+            "one training point": lambda: refused(lambda: svm.learn_held(one_left, S=S2, imax=IMAX)),
+        }
+        for name, call in calls.items():
+            call()
+            if not name.startswith(("a ", "one ")):
+                assert svm.iters_multi.min() > 0, name
+            if name.startswith("held, moved"):
+                assert np.array_equal(svm.pivots, [n - 2] * 2)
+            now = in_place()
+            assert np.array_equal(now[0], found[0]) and now[1] == found[1] and np.array_equal(now[2], found[2]), \
+                f"{name}: q or QA_cost in place are not as they were found"
+            assert same(solved(svm.learn(IMAX)), before), f"{name}: the context is not as it was found"
+        assert svm.info()["multi_width"] == (8 if multi_width is None else 1)
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_densified_csr_takes_held_lanes(dtype):
     """A CSR context forced to the densified path against the dense context on the same matrix (300 x 500, 10 entries per

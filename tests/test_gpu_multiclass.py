@@ -200,6 +200,27 @@ def test_learn_multi_with_graphs_off_and_on(graph, monkeypatch):
         _assert_learn_equal(svm, ref)
 
 
+def test_abi_learn_multi_is_learn_lanes():
+    """plssvm_mi_learn_multi stays in the ABI though CSVM.learn_multi goes through plssvm_mi_learn_lanes: called
+    directly on the two-tile setting, its alphas, biases, traces and iteration counts are learn_multi()'s bits."""
+    kernel, m, dtype, gamma, cost, eps = SETTINGS[5]
+    lab = _data(m, dtype)[1]
+    with _svm(kernel, m, dtype, gamma, cost, eps) as svm:
+        svm.learn_multi(lab, IMAX)
+        _, Y = pm.one_vs_all(lab, svm.dtype)
+        nk, n = Y.shape
+        alphas, biases = np.zeros((nk, n), dtype=svm.dtype), np.zeros(nk)
+        trace, it = np.full((nk, IMAX + 1), np.nan), np.zeros(nk, dtype=np.int64)
+        assert _abi.lib().plssvm_mi_learn_multi(svm._ctx, pm._ptr(Y), nk, n, IMAX, float(eps), pm._ptr(alphas), pm._ptr(biases),
+                                                pm._ptr(trace), pm._ptr(it)) == _abi.OK
+        assert nk == K and svm.iters_multi.min() > 0
+        assert np.array_equal(it, svm.iters_multi) and np.array_equal(alphas, svm.alphas)
+        assert np.array_equal(biases.astype(svm.dtype), svm.biases)
+        for k in range(nk):
+            assert np.array_equal(trace[k, : it[k] + 1], svm.traces[k])
+            assert np.isnan(trace[k, it[k] + 1:]).all()  # a row is filled up to iters[k]
+
+
 # ---- 3. chunking ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("width", [2, 1])
 def test_groups_of_the_width(width):
