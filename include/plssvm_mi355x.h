@@ -359,6 +359,31 @@ PLSSVM_MI_API int plssvm_mi_learn_held(plssvm_mi_ctx *ctx, const void *Y, int64_
  * is kept. */
 PLSSVM_MI_API int plssvm_mi_train_values(plssvm_mi_ctx *ctx, const void *ALPHA, int64_t nclass, int64_t lda,
                                          const double *bias, void *OUT, int64_t ldo);
+/* Gamma lanes (build-defined): a search over the width of the rbf or the laplacian kernel. Both are exp(-gamma dist_ij),
+ * and dist_ij is nearly all of a tile's work, so one pass over the implicit 128 x 128 tiles forms the distances once and
+ * serves up to 8 lanes (gamma_l, p_l) from them in registers. No kernel values are stored or read: the context's own
+ * gamma, cost, q, QA_cost and stored tiles are untouched by both calls (plssvm_mi_info.kp_cache_tiles stays).
+ * Lane l has its own q_i = k_{gamma_l}(x_i, x_m) and QA_cost = k_{gamma_l}(x_m, x_m) + diag_m; the context's point
+ * weights apply to every lane. Lane l is BITWISE the same call on a fresh context created with gamma = gammas[l] on the
+ * same data, whatever nlane, the lane's position or that context's tile cache. More lanes than the width
+ * (plssvm_mi_info.multi_width) run in groups, in order.
+ * Offered for dense data (plssvm_mi_setup_dense) with PLSSVM_MI_KERNEL_RBF or _LAPLACIAN on one GPU where the lanes are
+ * batched (the reference CG, PLSSVM_MI_OPT_MULTI_WIDTH != 1). Sparse data, the linear or polynomial kernel, a group, a
+ * simulated rank, the one-reduction CG: PLSSVM_MI_ERR_UNSUPPORTED, plssvm_mi_last_error names the reason, the context
+ * stays usable. No room for two lanes: PLSSVM_MI_ERR_OOM. nlane < 1, a gamma (or cost) that is not finite and > 0, a
+ * too small ld: PLSSVM_MI_ERR_ARG.
+ *
+ * plssvm_mi_kp_gammas: RET_l += add * Q~_{gamma_l} P_l for l < nlane (rows ld >= m apart), each row as plssvm_mi_kp
+ * with q NULL after plssvm_mi_generate_q on the fresh context. */
+PLSSVM_MI_API int plssvm_mi_kp_gammas(plssvm_mi_ctx *ctx, const double *gammas, const void *P, void *RET, int64_t nlane,
+                                      int64_t ld, double add);
+/* plssvm_mi_learn_gammas: lane l is plssvm_mi_set_cost(costs[l]) (costs NULL: the context's cost) and plssvm_mi_learn(y)
+ * on the fresh context: a (C, gamma) grid is one call with the caller's product of the two axes. alpha_out[nlane][n],
+ * bias_out[nlane], delta_trace (nullable) [nlane][imax + 1] filled up to iters[l], iters[nlane] (nullable); imax < 0: the
+ * number of features. Held-out points (plssvm_mi_learn_held) do not combine with gamma lanes. */
+PLSSVM_MI_API int plssvm_mi_learn_gammas(plssvm_mi_ctx *ctx, const void *y, const double *gammas, const double *costs,
+                                         int64_t nlane, int64_t imax, double eps, void *alpha_out, double *bias_out,
+                                         double *delta_trace, int64_t *iters);
 /* Timing hook: plssvm_mi_time_kp's K·p time for the product with nrhs resident vectors (in groups of the width; one at
  * a time where nothing is batched), averaged over `reps` products, measured with hipEvents on the context's stream. */
 PLSSVM_MI_API int plssvm_mi_time_kp_multi(plssvm_mi_ctx *ctx, int64_t nrhs, int reps, double *ms_per_kp);

@@ -576,6 +576,63 @@ class CSVM:
         y = np.ascontiguousarray(self.params.labels, dtype=self.dtype)
         return self._learn_lanes(np.ascontiguousarray(np.tile(y, (K, 1))), costs, S, imax, hold=H)
 
+    # ---- a search over the kernel width: gammas as lanes of one pass over the tiles (plssvm_mi_*_gammas) ----
+    @staticmethod
+    def _gammas(gammas):
+        g = np.atleast_1d(np.asarray(gammas, dtype=np.float64))
+        if g.ndim != 1 or g.size < 1 or not (np.isfinite(g).all() and (g > 0).all()):
+            raise ValueError("gammas must be a non-empty list of finite numbers > 0")
+        return np.ascontiguousarray(g)
+
+    def run_device_kernel_gammas(self, gammas, RET, P, add):
+        """RET[l] += add * Q~(gammas[l]) P[l] for the rbf or laplacian kernel on dense data: one pass over the tiles forms
+        every pair's distance once for all lanes. Row l is bitwise run_device_kernel (q=None, after generate_q) of a fresh
+        context with gamma = gammas[l]; this context's gamma, q and stored tiles are untouched."""
+        g = self._gammas(gammas)
+        assert RET.dtype == self.dtype and RET.flags.c_contiguous and RET.ndim == 2
+        PP = _rows(P, self.dtype, self.m, "P")
+        if PP.shape != RET.shape or PP.shape[0] != g.size:
+            raise ValueError("P and RET must have one row per gamma and the same shape")
+        if not self._on_device:
+            self.setup_data_on_device()
+        self._check(_abi.lib().plssvm_mi_kp_gammas(self._ctx, _ptr(g), _ptr(PP), _ptr(RET), g.size, PP.shape[1], float(add)))
+        return RET
+
+    def learn_gammas(self, gammas, costs=None, imax=-1):
+        """learn() at every (gammas[k], costs[k]) (costs None: the context's cost on every lane; a (C, gamma) grid is the
+        caller's product of the two axes), as lanes of one batched CG whose K.p forms each pair's distance once for all
+        lanes. Row k of alphas [K][n], biases [K], iters_multi, traces is bitwise set_cost(costs[k]); learn() of a fresh
+        context with gamma = gammas[k]. Sets gammas (and costs); the context's own gamma, cost and q stay."""
+        if self.params.labels is None:
+            raise ValueError("No labels given for training! Maybe the data is only usable for prediction?")
+        g = self._gammas(gammas)
+        cc = None
+        if costs is not None:
+            cc = np.ascontiguousarray(np.atleast_1d(np.asarray(costs, dtype=np.float64)))
+            if cc.shape != g.shape or not (np.isfinite(cc).all() and (cc > 0).all()):
+                raise ValueError(f"costs must be {g.size} finite numbers > 0, one per gamma")
+        s = self.params.point_weights()
+        if not self._on_device:
+            self.setup_data_on_device()
+        self._apply_class_weight(s)
+        y = np.ascontiguousarray(self.params.labels, dtype=self.dtype)
+        K, n = g.size, self.num_data_points
+        im = self.num_features if imax < 0 else imax
+        alphas = np.zeros((K, n), dtype=self.dtype)
+        biases = np.zeros(K, dtype=np.float64)
+        trace = np.full((K, im + 1), np.nan)
+        it = np.zeros(K, dtype=np.int64)
+        self._check(_abi.lib().plssvm_mi_learn_gammas(self._ctx, _ptr(y), _ptr(g), _ptr(cc), K, im, float(self.params.epsilon),
+                                                      _ptr(alphas), _ptr(biases), _ptr(trace), _ptr(it)))
+        self.alphas = alphas
+        self.biases = biases.astype(self.dtype)
+        self.iters_multi = it
+        self.traces = [trace[c, : it[c] + 1].copy() for c in range(K)]
+        self.gammas = g
+        if cc is not None:
+            self.costs = cc
+        return self
+
     def train_values(self, alphas=None, biases=None):
         """Decision values [n][K] of K models (default: alphas, biases as the last multi-lane learn left them) on the
         context's own n points, held-out ones included, from the kernel matrix the context already holds

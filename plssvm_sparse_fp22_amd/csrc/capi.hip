@@ -414,6 +414,25 @@ int plssvm_mi_train_values(plssvm_mi_ctx *ctx, const void *ALPHA, int64_t nclass
     });
 }
 
+int plssvm_mi_kp_gammas(plssvm_mi_ctx *ctx, const double *gammas, const void *P, void *RET, int64_t nlane, int64_t ld,
+                        double add) {
+    if (!ctx || !gammas || !P || !RET || nlane < 1) return PLSSVM_MI_ERR_ARG;
+    return ctx->call([&](auto &e) {
+        using T = std::remove_reference_t<decltype(e.gamma)>;
+        e.kp_gammas(gammas, static_cast<const T *>(P), static_cast<T *>(RET), nlane, ld, (T) add);
+    });
+}
+
+int plssvm_mi_learn_gammas(plssvm_mi_ctx *ctx, const void *y, const double *gammas, const double *costs, int64_t nlane,
+                           int64_t imax, double eps, void *alpha_out, double *bias_out, double *delta_trace, int64_t *iters) {
+    if (!ctx || !gammas || !alpha_out || nlane < 1) return PLSSVM_MI_ERR_ARG;
+    return ctx->call([&](auto &e) {
+        using T = std::remove_reference_t<decltype(e.gamma)>;
+        e.learn_gammas(static_cast<const T *>(y), gammas, costs, nlane, imax, (T) eps, static_cast<T *>(alpha_out), bias_out,
+                       delta_trace, iters);
+    });
+}
+
 int plssvm_mi_time_kp_multi(plssvm_mi_ctx *ctx, int64_t nrhs, int reps, double *ms_per_kp) {
     if (!ctx || nrhs < 1) return PLSSVM_MI_ERR_ARG;
     return ctx->call([&](auto &e) { e.time_kp_multi(nrhs, reps, ms_per_kp); });

@@ -527,6 +527,11 @@ T engine<T>::k_mm() const {
 }
 
 template <typename T>
+T engine<T>::k_mm_at(T g) const {
+    return host_kernel<T>(kernel, degree, g, coef0, xlast_h.data(), xlast_h.data(), d);
+}
+
+template <typename T>
 void engine<T>::generate_q(T *q_out, double *qa_out) {
     need_data();
     MI_HIP_CHECK(hipSetDevice(device));
@@ -569,7 +574,7 @@ void engine<T>::set_q(const T *q_host) {
 // rank's rows, then the gathered partials of all ranks)
 template <typename T>
 void engine<T>::kp_sums(const T *p, const cg_lane &L, const cg_scalars<T> *status) {
-    launch_dot2<T>(p + v0, nullptr, qf() + v0, p + v0, vn, L.red, status, stream);
+    launch_dot2<T>(p + v0, nullptr, lane_qf(L) + v0, p + v0, vn, L.red, status, stream);
     launch_dot_final<T>(gather_partials(L.red, 3), L.sc, FIN_SP_SQP, 0, nullptr, 0, nullptr, stream, G);
 }
 
@@ -581,7 +586,7 @@ void engine<T>::kp_slab_reduce(const cg_lane &L, const cg_scalars<T> *status) {
 template <typename T>
 void engine<T>::kp_fin(const cg_lane &L, const T *p, T *out, T add, bool overwrite, const cg_scalars<T> *status) {
     const int flags = (overwrite ? 1 : 0) | ((sim_world > 0 && sim_rank != 0 && !shard) ? 2 : 0);
-    launch_kp_finalize<T>(L.raw + v0, qf() + v0, p + v0, L.sc, L.QA, L.cost_inv, L.sinv ? L.sinv + v0 : nullptr,
+    launch_kp_finalize<T>(L.raw + v0, lane_qf(L) + v0, p + v0, L.sc, L.QA, L.cost_inv, L.sinv ? L.sinv + v0 : nullptr,
                           L.hold ? L.hold + v0 : nullptr, add, flags, vn, out + v0, status, stream);
 }
 
@@ -694,7 +699,7 @@ cg_scalars<T> engine<T>::cg_scalars_init(T eps, bool force) {
 template <typename T>
 void engine<T>::cg_fin_dad(const cg_lane &L, const T *v, T *pd, const T *slabs, int64_t P) {
     const int raw_only = (sim_world > 0 && sim_rank != 0 && !shard) ? 1 : 0;
-    launch_cg_fin_dad<T>(L.raw + v0, slabs, P, m, qf() + v0, v + v0, gathered ? cgp_g.get() : L.cgp, G, L.QA, L.cost_inv,
+    launch_cg_fin_dad<T>(L.raw + v0, slabs, P, m, lane_qf(L) + v0, v + v0, gathered ? cgp_g.get() : L.cgp, G, L.QA, L.cost_inv,
                          L.sinv ? L.sinv + v0 : nullptr, L.hold ? L.hold + v0 : nullptr, raw_only, vn, L.Ad + v0, pd, L.sc,
                          stream);
 }
@@ -724,7 +729,7 @@ template <typename T>
 void engine<T>::cg_dir(const cg_lane &L, int init) {
     dir_w_t<T> wo{};
     const bool fw = dir_w_fill(wo);
-    launch_cg_dir_sums<T>(L.d + v0, L.r + v0, qf() + v0, init ? nullptr : gather_partials(L.prr(), 2), init ? 1 : G, init,
+    launch_cg_dir_sums<T>(L.d + v0, L.r + v0, lane_qf(L) + v0, init ? nullptr : gather_partials(L.prr(), 2), init ? 1 : G, init,
                           init ? nullptr : L.trace, init ? 0 : L.trace_cap, vn, L.cgp, L.sc, stream, fw ? &wo : nullptr);
     w_pre = fw ? L.d : nullptr;
 }

@@ -273,6 +273,7 @@ struct engine : engine_base {
         cg_scalars<T> *sc;
         double *trace;
         int64_t trace_cap;
+        const T *q = nullptr;  // the lane's own q (a gamma lane); null: the engine's qf()
         T *pdad() const { return cgp + 2 * RED_BLOCKS; }
         T *prr() const { return cgp + 4 * RED_BLOCKS; }
     };
@@ -285,8 +286,9 @@ struct engine : engine_base {
         return { dg.cost_inv, dg.QA, dg.sinv, dg.hold, lane_v(LV_X, c), lane_v(LV_R, c), lane_v(LV_D, c), lane_v(LV_AD, c),
                  lane_v(LV_B, c), lane_v(LV_RAW, c), lane_cgp(c), lane_red(c),
                  lanes.slab.get() + (int64_t) c * lanes.sstride, lanes.sc.get() + c,
-                 lanes.trace.get() + (int64_t) c * lanes.trace_cap, lanes.trace_cap };
+                 lanes.trace.get() + (int64_t) c * lanes.trace_cap, lanes.trace_cap, dg.q };
     }
+    const T *lane_qf(const cg_lane &L) const { return L.q != nullptr ? L.q : qf(); }  // the q the lane's steps read
     // The steps take the rows [v0, v0 + vn), sum the G ranks' partials (gather_partials) and use qf() / QAf() /
     // dir_w_fill as the single solve needs them in a group, sharded or on the stored sparse paths. For a pool lane
     // all of that is the identity — multi_batched(): the tile path on one rank, no shard, no simulated rank, the
@@ -337,6 +339,7 @@ struct engine : engine_base {
         T cost_inv, QA;
         const T *sinv;
         const uint8_t *hold;
+        const T *q = nullptr;  // a gamma lane's own q_i = k_gamma(x_i, x_m) (lane_pool::q); null: the engine's
     };
     struct lane_pool {
         // every lane's diagonal (cg_lane), set by the batched entry points before they run a group: the engine's own
@@ -346,6 +349,9 @@ struct engine : engine_base {
                                            // per-lane weights (need_lane_buf), never for lanes that differ in C only
         dev_buf<uint8_t> hold;             // [width][vstride] per-lane held-row flags: allocated by the first learn_held
                                            // call that passes them (need_lane_buf)
+        dev_buf<T> q;                      // [width][vstride] per-lane q: allocated by the first gamma-lane call
+        std::vector<T> gam;                // the running gamma group's gamma per lane; empty: the lanes share the
+                                           // engine's kernel values (tiles_multi picks the tile launch by it)
         int width = 0;                     // lanes allocated: 0 = not yet, 1 = none fit (one at a time)
         int64_t vstride = 0, sstride = 0;  // elements between two lanes' vectors / slabs
         dev_buf<T> vec;                    // [LV_COUNT][width][vstride], zero padded like the engine's vectors
@@ -355,7 +361,7 @@ struct engine : engine_base {
         dev_buf<double> trace;             // [width][trace_cap]
         int64_t trace_cap = 0;
         int64_t bytes() const {
-            return vec.bytes() + slab.bytes() + part.bytes() + sc.bytes() + trace.bytes() + sinv.bytes() + hold.bytes();
+            return vec.bytes() + slab.bytes() + part.bytes() + sc.bytes() + trace.bytes() + sinv.bytes() + hold.bytes() + q.bytes();
         }
     };
     enum lane_vec { LV_X = 0, LV_R, LV_D, LV_AD, LV_B, LV_RAW, LV_COUNT };
@@ -379,6 +385,7 @@ struct engine : engine_base {
     bool need_lane_buf(dev_buf<U> &buf);
     T *lane_sinv(int c) const { return lanes.sinv.get() + (int64_t) c * lanes.vstride; }
     uint8_t *lane_hold(int c) const { return lanes.hold.get() + (int64_t) c * lanes.vstride; }
+    T *lane_q(int c) const { return lanes.q.get() + (int64_t) c * lanes.vstride; }
     // The batched launch streams filled records only: if the tile cache is allocated and unfilled, `product` (a K·p of
     // the caller's choice on the single path, after sc is zeroed) fills it; true if it ran
     template <typename F>
@@ -397,7 +404,8 @@ struct engine : engine_base {
     void kp_lanes(int kin, int kout, int c0, int nvec, T add, bool overwrite, bool flags, bool then_rr = false);
     void cg_iter_multi(int nvec, int reset);
     // held: the lanes' diag carries hold rows — x0 is the lane's own (1 on its active rows), so the first residual goes
-    // through kp_lanes per lane instead of the shared first product
+    // through kp_lanes per lane instead of the shared first product; so it does for gamma lanes (lanes.gam), whose
+    // kernel values are their own
     void solve_cg_group(const T *B, int nvec, int64_t ld, int64_t imax, T eps, T *X_out, double *trace_out, int64_t *iters,
                         bool held = false);
     void solve_cg_multi(const T *B, int64_t nrhs, int64_t ld, const T *q_host, int64_t imax, T eps, T *X_out,
@@ -440,6 +448,19 @@ struct engine : engine_base {
     // caller's q is replaced, QA_cost is kept).
     void train_values(const T *ALPHA, int64_t nclass, int64_t lda, const double *bias, T *OUT, int64_t ldo);
     void time_kp_multi(int64_t nrhs, int reps, double *ms_kp);
+    // ---- gamma lanes (plssvm_mi_kp_gammas / _learn_gammas, kp_gamma.hip) ----
+    // A lane is (gamma_l, C_l): its kernel values exp(-gamma_l dist) come from the tile's distances, formed once per tile
+    // for the whole group and never stored; its q (lane_pool::q, one pass over X per group) and QA = k_mm + diag_m are its
+    // own. The steps are the pool lanes' (the context's point weights apply to every lane), so lane l is bitwise a fresh
+    // context with gamma_l. Dense data with the rbf or laplacian kernel where the lanes are batched (multi_batched() and
+    // room for the pool): everything else is ERR_UNSUPPORTED with the reason. Neither call moves the engine's gamma,
+    // cost, q, QA_cost or tile cache. K > width: groups of the width, in order.
+    int gamma_pool();                                        // the checks; the pool with its q buffer; returns the width
+    void gamma_group(const double *gammas, const T *costs, int nvec);  // lanes.gam, the lanes' q and diag for one group
+    T k_mm_at(T g) const;                                    // k_mm() at another gamma
+    void kp_gammas(const double *gammas, const T *P, T *RET, int64_t nlane, int64_t ld, T add);
+    void learn_gammas(const T *y, const double *gammas, const double *costs, int64_t nlane, int64_t imax, T eps, T *alpha_out,
+                      double *bias_out, double *trace_out, int64_t *iters);
 
     // sparse paths (sparse.hip)
     void sparse_q();                                              // q, norms, e on CSR data

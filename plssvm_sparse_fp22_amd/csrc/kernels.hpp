@@ -159,6 +159,19 @@ template <typename T>
 void launch_kp_tiles_multi(const kp_geom<T> &g, const T *p, int64_t pstride, T *partial, int64_t sstride, int nvec,
                            const cg_scalars<T> *status, hipStream_t s, const kp_cache_view<T> &kc = {});
 
+// Gamma lanes (kp_gamma.hip): the tiles of g (rbf or laplacian; g.kf.gamma is not read) for nvec <=
+// KP_MULTI_W pairs (gammas[c], p + c * pstride) at once, always implicit. A tile's distances are formed once and every
+// lane's kernel values come from them in registers: slab c (partial + c * sstride) is bitwise launch_kp_tiles' slab
+// for p_c on a context with gamma = gammas[c]. gammas: nvec host values. status as for launch_kp_tiles_multi.
+template <typename T>
+void launch_kp_tiles_gamma(const kp_geom<T> &g, const T *gammas, const T *p, int64_t pstride, T *partial, int64_t sstride,
+                           int nvec, const cg_scalars<T> *status, hipStream_t s);
+// q_c[i] = k_{gammas[c]}(x_i, x_last), i < m, into q + c * qstride for c < nvec in one pass over X; row c is bitwise
+// launch_q_dense at that gamma
+template <typename T>
+void launch_q_gammas(int kernel, const T *gammas, int nvec, const T *XT, int64_t n_pad, int64_t d, int64_t m, const T *xlast,
+                     T *q, int64_t qstride, hipStream_t s);
+
 // ---- fused dense predict tiles (predict_tiles.hip) -------------------------------------------------
 // One workgroup owns a 128-point tile and one segment of PRED_SEG consecutive 128-row support-vector tiles. The
 // segment length is a compile-time constant: it fixes the summation order of a decision value, which therefore

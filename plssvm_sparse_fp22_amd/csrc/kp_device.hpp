@@ -1,4 +1,4 @@
-// Device helpers shared by the MFMA tile kernels (kp_tiles.hip, predict_tiles.hip): the kernel function on an
+// Device helpers shared by the MFMA tile kernels (kp_tiles.hip, kp_gamma.hip, predict_tiles.hip): the kernel function on an
 // accumulator value, the table-driven fp64 exp of the RBF epilogue and the global -> LDS DMA of the K loop.
 #pragma once
 
@@ -176,6 +176,37 @@ __device__ __forceinline__ void glds16_buf(const void *base, void *lds_dst, uint
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *) base, (short) 0, 0x7FFFFFFF, 0x00020000);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void *) lds_dst, 16, voff, soff, 0, 0);
 }
+
+// ---- shared by the pairwise tile kernels of kp_tiles.hip and kp_gamma.hip ----
+// fp64 RBF: chunk kc+1's DMA is issued after chunk kc's LDS reads; every other instance: right after the barrier.
+// Same box, round 6 (profiles/r06_kp_dma_order_ab.json): config 2 (fp64 RBF) 39.51 / 39.58 ms against 39.62 / 39.67 ms
+// with the DMA first; fp64 linear 37.18 / 37.23 against 36.67 / 36.67 ms, fp64 poly 38.72 / 38.76 against 38.58 /
+// 38.58 ms, configs[3] (fp32 linear) 1 913 against 1 782 ms. KP_DMA_AFTER_READS=0 / 1 forces one order (A/B only)
+#ifndef KP_DMA_AFTER_READS
+#define KP_DMA_AFTER_READS 2
+#endif
+template <typename T, int KERNEL>
+constexpr bool kp_dma_after_reads() {
+    if (KERNEL == KF_LAPLACIAN) return true;  // behind the chunk's last LDS reads (its K loop reads feature by feature)
+    return KP_DMA_AFTER_READS == 2 ? (sizeof(T) == 8 && KERNEL == 2) : KP_DMA_AFTER_READS == 1;
+}
+
+// The slab is written once by the tile kernels and read once by kp_reduce_share_kernel: the tile kernels' slab stores
+// and the reduce's slab loads carry the non-temporal hint as well. -DKP_SLAB_NT=0 builds both plain (A/B in DESIGN.md
+// §3.1.2: the slab pass takes 107 us with the hint and 155 us without)
+#ifndef KP_SLAB_NT
+#define KP_SLAB_NT 1
+#endif
+template <typename T>
+__device__ __forceinline__ void kp_slab_store(T *at, T v) {
+    if constexpr (KP_SLAB_NT != 0) __builtin_nontemporal_store(v, at);
+    else *at = v;
+}
+
+// LDS layout of the epilogue's reduction buffers (element counts): p_I, p_J, n_I, n_J, then row partials
+// [wc][128 rows][16 (+1 pad)] and column partials [wr][128 cols][4 (+1 pad)]
+constexpr int KP_OFF_PAN = 4 * KP_TILE;
+constexpr int KP_RSTR = 17, KP_RHALF = KP_TILE * KP_RSTR + 1, KP_CSTR = 5;
 
 }  // namespace
 

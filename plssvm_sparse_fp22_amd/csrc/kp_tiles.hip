@@ -36,19 +36,6 @@ namespace {
 template <typename T, int KERNEL>
 constexpr int kp_waves_per_eu() { return (KERNEL == KF_LAPLACIAN && sizeof(T) == 8) ? 2 : 3; }
 
-// fp64 RBF: chunk kc+1's DMA is issued after chunk kc's LDS reads; every other instance: right after the barrier.
-// Same box, round 6 (profiles/r06_kp_dma_order_ab.json): config 2 (fp64 RBF) 39.51 / 39.58 ms against 39.62 / 39.67 ms
-// with the DMA first; fp64 linear 37.18 / 37.23 against 36.67 / 36.67 ms, fp64 poly 38.72 / 38.76 against 38.58 /
-// 38.58 ms, configs[3] (fp32 linear) 1 913 against 1 782 ms. KP_DMA_AFTER_READS=0 / 1 forces one order (A/B only)
-#ifndef KP_DMA_AFTER_READS
-#define KP_DMA_AFTER_READS 2
-#endif
-template <typename T, int KERNEL>
-constexpr bool kp_dma_after_reads() {
-    if (KERNEL == KF_LAPLACIAN) return true;  // behind the chunk's last LDS reads (its K loop reads feature by feature)
-    return KP_DMA_AFTER_READS == 2 ? (sizeof(T) == 8 && KERNEL == 2) : KP_DMA_AFTER_READS == 1;
-}
-
 // KP_LOAD streams a tile's stored kernel values instead of forming them: no K loop, LDS = the reduction buffers
 // only. Workgroups per CU (= waves per SIMD): KP_LOAD_WAVES, default 3 in fp64 (128 of <= 168 VGPRs hold the
 // tile's values: 3 x 128 KiB of loads in flight per CU) and 4 in fp32; A/B in DESIGN.md §3.1.2
@@ -87,23 +74,6 @@ struct kp_vec<float> {
 #ifndef KP_LOAD_NT
 #define KP_LOAD_NT 1
 #endif
-// The slab is written once by the tile kernels and read once by kp_reduce_share_kernel: the tile kernels' slab stores
-// and the reduce's slab loads carry the non-temporal hint as well. -DKP_SLAB_NT=0 builds both plain (A/B in DESIGN.md
-// §3.1.2: the slab pass takes 107 us with the hint and 155 us without)
-#ifndef KP_SLAB_NT
-#define KP_SLAB_NT 1
-#endif
-template <typename T>
-__device__ __forceinline__ void kp_slab_store(T *at, T v) {
-    if constexpr (KP_SLAB_NT != 0) __builtin_nontemporal_store(v, at);
-    else *at = v;
-}
-
-// LDS layout of the epilogue's reduction buffers (element counts): p_I, p_J, n_I, n_J, then row partials
-// [wc][128 rows][16 (+1 pad)] and column partials [wr][128 cols][4 (+1 pad)]
-constexpr int KP_OFF_PAN = 4 * KP_TILE;
-constexpr int KP_RSTR = 17, KP_RHALF = KP_TILE * KP_RSTR + 1, KP_CSTR = 5;
-
 // The fp64 KP_LOAD workgroup: the tile's record -> registers -> the "times p" epilogue of kp_tile_kernel (the same
 // fma chains, LDS park and fixed-order sums, so the slab record is bitwise the computed one). FORM: KP_FORM_WIDE and
 // KP_FORM_NARROW, the record is a packed one of kp_record.hpp with 24-bit or 21-bit fields — 28 dwordx4 per lane, or

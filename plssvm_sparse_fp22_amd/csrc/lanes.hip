@@ -108,6 +108,12 @@ void engine<T>::lanes_own_diag() {
 // The stored records are streamed once they are filled; filling them is the single-vector path's job.
 template <typename T>
 void engine<T>::tiles_multi(int kind, int c0, int nvec, bool flags) {
+    if (!lanes.gam.empty()) {  // gamma lanes: their own kernel values from the tile's distances, never stored ones
+        launch_kp_tiles_gamma<T>(kp_geometry(), lanes.gam.data() + c0, lane_v(kind, c0), lanes.vstride,
+                                 lanes.slab.get() + (int64_t) c0 * lanes.sstride, lanes.sstride, nvec,
+                                 flags ? lanes.sc.get() + c0 : nullptr, stream);
+        return;
+    }
     launch_kp_tiles_multi<T>(kp_geometry(), lane_v(kind, c0), lanes.vstride, lanes.slab.get() + (int64_t) c0 * lanes.sstride,
                              lanes.sstride, nvec, flags ? lanes.sc.get() + c0 : nullptr, stream, kc.view());
 }
@@ -148,6 +154,7 @@ template <typename T>
 void engine<T>::solve_cg_group(const T *B, int nvec, int64_t ld, int64_t imax, T eps, T *X_out, double *trace_out,
                                int64_t *iters, bool held) {
     need_pool();
+    const bool own_x0 = held || !lanes.gam.empty();  // the first product is each lane's own
     // cg_begin per lane
     const cg_scalars<T> init = cg_scalars_init(eps, false);
     const std::vector<cg_scalars<T>> inits((size_t) nvec, init);
@@ -164,8 +171,9 @@ void engine<T>::solve_cg_group(const T *B, int nvec, int64_t ld, int64_t imax, T
         if (held) launch_cg_init_held<T>(lane_v(LV_B, c), lanes.diag[(size_t) c].hold, m, lane_v(LV_X, c), lane_v(LV_R, c), stream);
         else launch_cg_init<T>(lane_v(LV_B, c), m, lane_v(LV_X, c), lane_v(LV_R, c), stream);  // x = 1; r = b
     }
-    if (held) {
-        // x0 = 1 on the lane's own active rows: r -= Q~x per lane, one pass over the (filled) tiles for the group
+    if (own_x0) {
+        // x0 = 1 on the lane's own active rows (gamma lanes: every row, under the lane's own kernel values): r -= Q~x per
+        // lane, one pass over the (filled) tiles for the group
         kp_lanes(LV_X, LV_R, 0, nvec, T(-1), false, false);
     } else {
         // r -= Q~x: x0 = 1 is the same for every lane, so kp_device's first half runs once, on the engine's own buffers
@@ -176,7 +184,7 @@ void engine<T>::solve_cg_group(const T *B, int nvec, int64_t ld, int64_t imax, T
     }
     for (int c = 0; c < nvec; ++c) {
         const cg_lane L = pool_lane(c);
-        if (!held) {
+        if (!own_x0) {
             cg_lane S = own_lane();  // the shared raw and sums, the lane's diagonal
             S.cost_inv = L.cost_inv, S.QA = L.QA, S.sinv = L.sinv;
             kp_fin(S, L.x, L.r, T(-1), false, nullptr);
@@ -447,6 +455,139 @@ void engine<T>::learn_held(const T *Y, int64_t nlane, int64_t ldy, const double 
     restore();
 }
 
+// ---- gamma lanes (engine.hpp) ---------------------------------------------------------------------
+template <typename T>
+int engine<T>::gamma_pool() {
+    need_data();
+    const char *why = (kernel != 2 && kernel != KF_LAPLACIAN) ? "a kernel without a distance that all gammas share (linear, polynomial)"
+                      : sparse                                ? "sparse (CSR) data"
+                      : (sim_world > 0)                       ? "a simulated rank"
+                      : (world > 1 || comm != nullptr || xchg != nullptr || shard) ? "a multi-GPU group"
+                      : cg1_wanted()                          ? "the one-reduction CG"
+                      : !held_supported()                     ? "a setup without kernel-matrix tiles"
+                      : multi_opt == 1                        ? "set to one vector at a time (PLSSVM_MI_OPT_MULTI_WIDTH = 1)"
+                                                              : nullptr;
+    if (why != nullptr)
+        throw mi_error(-5, std::string("gamma lanes run on dense data with the rbf or laplacian kernel, on one GPU with the "
+                                       "batched reference CG; this context is ") + why + " (use one context per gamma instead)");
+    MI_HIP_CHECK(hipSetDevice(device));
+    const int W = multi_lanes();
+    if (W < 2 || !need_lane_buf(lanes.q)) throw mi_error(-4, "no device memory for two gamma lanes (use one context per gamma instead)");
+    need_pool();
+    return W;
+}
+
+template <typename T>
+void engine<T>::gamma_group(const double *gammas, const T *costs, int nvec) {
+    lanes.gam.assign(gammas, gammas + nvec);  // rounded to T as plssvm_mi_create rounds a context's gamma
+    launch_q_gammas<T>(kernel, lanes.gam.data(), nvec, XT.get(), n_pad, d, m, xlast.get(), lanes.q.get(), lanes.vstride, stream);
+    for (int c = 0; c < nvec; ++c) {
+        const T cl = costs != nullptr ? costs[c] : cost;
+        lanes.diag[(size_t) c] = lane_diag{ T(1) / cl, lane_QA(k_mm_at(lanes.gam[(size_t) c]), cl, weighted() ? sinv_h.data() : nullptr, m),
+                                            sinv_dev(), nullptr, lane_q(c) };
+    }
+}
+
+namespace {
+// every gamma a finite number > 0, also once rounded to T
+template <typename T>
+void check_gammas(const double *gammas, int64_t nlane) {
+    if (gammas == nullptr || nlane < 1) throw mi_error(-1, "at least one gamma is needed");
+    for (int64_t k = 0; k < nlane; ++k) {
+        const T g = (T) gammas[k];
+        if (!(gammas[k] > 0) || !std::isfinite(gammas[k]) || !(g > T(0)) || !std::isfinite(g))
+            throw mi_error(-1, "gamma " + std::to_string(k) + " is not a finite number > 0");
+    }
+}
+}  // namespace
+
+// RET_l += add * Q~_{gamma_l} P_l, each lane with its own q and QA_cost at the context's cost and weights
+template <typename T>
+void engine<T>::kp_gammas(const double *gammas, const T *P, T *RET, int64_t nlane, int64_t ld, T add) {
+    need_data();
+    check_gammas<T>(gammas, nlane);
+    if (P == nullptr || RET == nullptr) throw mi_error(-1, "kp_gammas needs P and RET");
+    if (ld < m) throw mi_error(-1, "the leading dimension is smaller than the number of rows");
+    const int W = gamma_pool();
+    cg_active = false;
+    auto run = [&]() {
+        for (int64_t c0 = 0; c0 < nlane; c0 += W) {
+            const int nvec = (int) std::min<int64_t>(W, nlane - c0);
+            MI_HIP_CHECK(hipMemsetAsync(lanes.sc.get(), 0, sizeof(cg_scalars<T>) * (size_t) nvec, stream));
+            gamma_group(gammas + c0, nullptr, nvec);
+            for (int c = 0; c < nvec && m > 0; ++c) {
+                MI_HIP_CHECK(hipMemcpyAsync(lane_v(LV_D, c), P + (c0 + c) * ld, sizeof(T) * (size_t) m, hipMemcpyHostToDevice, stream));
+                MI_HIP_CHECK(hipMemcpyAsync(lane_v(LV_R, c), RET + (c0 + c) * ld, sizeof(T) * (size_t) m, hipMemcpyHostToDevice, stream));
+            }
+            if (m > 0) kp_lanes(LV_D, LV_R, 0, nvec, add, false, false);
+            for (int c = 0; c < nvec && m > 0; ++c)
+                MI_HIP_CHECK(hipMemcpyAsync(RET + (c0 + c) * ld, lane_v(LV_R, c), sizeof(T) * (size_t) m, hipMemcpyDeviceToHost, stream));
+            MI_HIP_CHECK(hipStreamSynchronize(stream));
+        }
+    };
+    try {
+        run();
+    } catch (...) {
+        lanes.gam.clear();
+        lanes_own_diag();
+        throw;
+    }
+    lanes.gam.clear();
+    lanes_own_diag();
+}
+
+// Lane k = a fresh context with gamma = gammas[k], set_cost(costs[k]) (null: the engine's cost), the engine's point
+// weights, learn(y): b = y - y_m, the reference CG from x0 = 1 as a pool lane, learn()'s end with the lane's q and QA
+template <typename T>
+void engine<T>::learn_gammas(const T *y, const double *gammas, const double *costs, int64_t nlane, int64_t imax, T eps,
+                             T *alpha_out, double *bias_out, double *trace_out, int64_t *iters) {
+    need_data();
+    check_gammas<T>(gammas, nlane);
+    if (alpha_out == nullptr) throw mi_error(-1, "learn_gammas needs an alpha output");
+    // the labels and costs checked as learn_lanes checks them; every lane has the one label row y and the pivot m
+    const lane_plan<T> plan(n, cost, y, nlane, n, costs, nullptr, 0, nullptr, 0);
+    const int W = gamma_pool();
+    if (imax < 0) imax = d;
+    const int64_t cap = imax + 1;
+    cg_active = false;  // a group borrows the single solve's scalars
+    auto run = [&]() {
+        std::vector<T> b1((size_t) n, T(0));
+        plan.stage(plan.lanes[0], y, nullptr, b1.data());
+        for (int64_t k0 = 0; k0 < nlane; k0 += W) {
+            const int nvec = (int) std::min<int64_t>(W, nlane - k0);
+            std::vector<T> cl((size_t) nvec), bh((size_t) nvec * (size_t) n), xt((size_t) nvec * (size_t) n, T(0)), qh((size_t) nvec * (size_t) std::max<int64_t>(m, 1));
+            std::vector<double> tr(trace_out ? (size_t) (nvec * cap) : 0);
+            std::vector<int64_t> it((size_t) nvec);
+            for (int c = 0; c < nvec; ++c) {
+                cl[(size_t) c] = plan.lanes[(size_t) (k0 + c)].cost;
+                std::copy(b1.begin(), b1.end(), bh.begin() + (int64_t) c * n);
+            }
+            gamma_group(gammas + k0, cl.data(), nvec);
+            for (int c = 0; c < nvec && m > 0; ++c)
+                MI_HIP_CHECK(hipMemcpyAsync(qh.data() + (int64_t) c * m, lane_q(c), sizeof(T) * (size_t) m, hipMemcpyDeviceToHost, stream));
+            solve_cg_group(bh.data(), nvec, n, imax, eps, xt.data(), trace_out ? tr.data() : nullptr, it.data(), false);
+            for (int c = 0; c < nvec; ++c) {
+                const int64_t k = k0 + c;
+                T *a = alpha_out + k * n;
+                std::copy(xt.begin() + (int64_t) c * n, xt.begin() + (int64_t) c * n + m, a);
+                a[m] = T(0);
+                learn_tail(y, qh.data() + (int64_t) c * m, lanes.diag[(size_t) c].QA, m, m, a, bias_out ? bias_out + k : nullptr);
+                if (iters) iters[k] = it[(size_t) c];
+                if (trace_out) std::copy_n(tr.begin() + (int64_t) c * cap, std::min<int64_t>(cap, it[(size_t) c] + 1), trace_out + k * cap);
+            }
+        }
+    };
+    try {
+        run();
+    } catch (...) {
+        lanes.gam.clear();
+        lanes_own_diag();
+        throw;
+    }
+    lanes.gam.clear();
+    lanes_own_diag();
+}
+
 template <typename T>
 void engine<T>::train_values(const T *ALPHA, int64_t nclass, int64_t lda, const double *bias, T *OUT, int64_t ldo) {
     need_data();
@@ -572,7 +713,12 @@ void engine<T>::time_kp_multi(int64_t nrhs, int reps, double *ms_kp) {
     template void engine<T>::learn_held(const T *, int64_t, int64_t, const double *, const T *, int64_t, const uint8_t *, \
                                         int64_t, int64_t, T, T *, double *, double *, int64_t *, int64_t *);         \
     template void engine<T>::train_values(const T *, int64_t, int64_t, const double *, T *, int64_t);                \
-    template void engine<T>::time_kp_multi(int64_t, int, double *);
+    template void engine<T>::time_kp_multi(int64_t, int, double *);                                                  \
+    template int engine<T>::gamma_pool();                                                                            \
+    template void engine<T>::gamma_group(const double *, const T *, int);                                            \
+    template void engine<T>::kp_gammas(const double *, const T *, T *, int64_t, int64_t, T);                         \
+    template void engine<T>::learn_gammas(const T *, const double *, const double *, int64_t, int64_t, T, T *, double *, \
+                                          double *, int64_t *);
 INST(float)
 INST(double)
 #undef INST
