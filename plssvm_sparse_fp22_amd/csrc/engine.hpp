@@ -291,10 +291,10 @@ struct engine : engine_base {
     const T *lane_qf(const cg_lane &L) const { return L.q != nullptr ? L.q : qf(); }  // the q the lane's steps read
     // The steps take the rows [v0, v0 + vn), sum the G ranks' partials (gather_partials) and use qf() / QAf() /
     // dir_w_fill as the single solve needs them in a group, sharded or on the stored sparse paths. For a pool lane
-    // all of that is the identity — multi_batched(): the tile path on one rank, no shard, no simulated rank, the
-    // reference recurrence, so v0 = 0, vn = m, G = 1, gather_partials returns its argument, ctr_active() and
-    // dir_w_fill() are false (need_pool checks it at the batched entry points). status: the stop flag the kernels
-    // leave at, nullptr = none.
+    // all of that is the identity — multi_batched(): the tile path or the sparse on-the-fly path on one rank, no shard,
+    // no simulated rank, the reference recurrence, so v0 = 0, vn = m, G = 1, gather_partials returns its argument,
+    // ctr_active() and dir_w_fill() are false (need_pool checks it at the batched entry points). status: the stop flag
+    // the kernels leave at, nullptr = none.
     void kp_sums(const T *p, const cg_lane &L, const cg_scalars<T> *status);  // sum p, sum q p -> L.sc (through L.red)
     void kp_slab_reduce(const cg_lane &L, const cg_scalars<T> *status);       // L.slab -> L.raw
     // out = (overwrite ? 0 : out) + add * Q~ p from L.raw and L.sc's sums (a group's shared first product: the
@@ -333,8 +333,11 @@ struct engine : engine_base {
     // side alone by construction. lane_v / lane_cgp / lane_red and LV_* are for pool_lane and the strided base of the
     // batched tile launch only. The single-solve members above are not touched by a batched group except sc, red,
     // raw and partial (the shared first product Q~ x0, x0 = 1).
-    // Batched: the pairwise tile path on one rank (multi_batched); everywhere else, and when not even two lanes fit
-    // in device memory, the same entry points run the right-hand sides one after another through solve_cg / kp_host.
+    // Batched (multi_batched): the pairwise tile path on one rank, and the sparse on-the-fly path on one rank, where the
+    // one pass is over the pairs (otf_pairs_lanes: s_ij and c_ij formed once for the group) and a
+    // lane's raw gets its separable part from otf_base instead of a slab reduce; everywhere else — the stored sparse
+    // paths, groups, shards, simulated ranks — and when not even two lanes fit in device memory, the same entry points
+    // run the right-hand sides one after another through solve_cg / kp_host.
     struct lane_diag {
         T cost_inv, QA;
         const T *sinv;
@@ -355,13 +358,16 @@ struct engine : engine_base {
         int width = 0;                     // lanes allocated: 0 = not yet, 1 = none fit (one at a time)
         int64_t vstride = 0, sstride = 0;  // elements between two lanes' vectors / slabs
         dev_buf<T> vec;                    // [LV_COUNT][width][vstride], zero padded like the engine's vectors
-        dev_buf<T> slab;                   // [width][sstride = kp_wgs * KP_REC]
+        dev_buf<T> slab;                   // [width][sstride = kp_wgs * KP_REC]; the on-the-fly path has none (sstride 0)
+        dev_buf<T> pk;                     // on-the-fly path: the group's vectors interleaved, [m][otf_lanes_nv(width)]
+        dev_buf<T> ssc;                    // on-the-fly path: [width][2], a lane's sum e p / sum p (otf_base)
         dev_buf<T> part;                   // [width][8 RED_BLOCKS]: a lane's cgp (6 R), then its red (2 R)
         dev_buf<cg_scalars<T>> sc;         // [width]
         dev_buf<double> trace;             // [width][trace_cap]
         int64_t trace_cap = 0;
         int64_t bytes() const {
-            return vec.bytes() + slab.bytes() + part.bytes() + sc.bytes() + trace.bytes() + sinv.bytes() + hold.bytes() + q.bytes();
+            return vec.bytes() + slab.bytes() + pk.bytes() + ssc.bytes() + part.bytes() + sc.bytes() + trace.bytes() + sinv.bytes() +
+                   hold.bytes() + q.bytes();
         }
     };
     enum lane_vec { LV_X = 0, LV_R, LV_D, LV_AD, LV_B, LV_RAW, LV_COUNT };
@@ -370,9 +376,12 @@ struct engine : engine_base {
     T *lane_v(int kind, int c) const { return lanes.vec.get() + ((int64_t) kind * lanes.width + c) * lanes.vstride; }
     T *lane_cgp(int c) const { return lanes.part.get() + (int64_t) c * 8 * RED_BLOCKS; }
     T *lane_red(int c) const { return lane_cgp(c) + 6 * RED_BLOCKS; }
-    // where the lanes' steps are the single solve's (the tile path on one rank with the reference CG): held-out lanes
-    // are offered there; batched there unless multi_opt == 1 (and given memory for two lanes)
+    // where the lanes' steps are the single solve's: one rank with the reference CG (one_rank_reference) on the tile
+    // path — held-out lanes, train_values' batched pass and gamma lanes are offered there (held_supported) — or on the
+    // sparse on-the-fly path (otf_lanes_ok); batched on either unless multi_opt == 1 (and given memory for two lanes)
+    bool one_rank_reference() const;
     bool held_supported() const;
+    bool otf_lanes_ok() const;
     bool multi_batched() const;
     // device memory of one lane (with_sinv: and its weight vector; with_hold: and its held-row flags)
     int64_t lane_bytes(bool with_sinv = false, bool with_hold = false) const;
@@ -386,6 +395,7 @@ struct engine : engine_base {
     T *lane_sinv(int c) const { return lanes.sinv.get() + (int64_t) c * lanes.vstride; }
     uint8_t *lane_hold(int c) const { return lanes.hold.get() + (int64_t) c * lanes.vstride; }
     T *lane_q(int c) const { return lanes.q.get() + (int64_t) c * lanes.vstride; }
+    T *lane_ssc(int c) const { return lanes.ssc.get() + 2 * c; }
     // The batched launch streams filled records only: if the tile cache is allocated and unfilled, `product` (a K·p of
     // the caller's choice on the single path, after sc is zeroed) fills it; true if it ran
     template <typename F>
@@ -398,8 +408,13 @@ struct engine : engine_base {
     void lanes_own_diag();                // every lane: the engine's own cost, QA_cost and weights
     void need_pool();                     // the steps' group / shard / centring handling is the identity here
     void tiles_multi(int kind, int c0, int nvec, bool flags);  // one pass over the tiles for lanes [c0, c0 + nvec)
+    // The lanes' pairwise part on the pool's path. pairs_multi: one pass for the vectors `kind` of lanes [c0, c0 + nvec),
+    // over the tiles (tiles_multi) or over the pairs (otf_pairs_lanes, into the lanes' raw). lane_raw: lane c's raw
+    // completed — summed from its slab (kp_slab_reduce) or, on the on-the-fly path, its separable part added (otf_base)
+    void pairs_multi(int kind, int c0, int nvec, bool flags);
+    void lane_raw(int kind, int c, const cg_scalars<T> *status);
     // vectors `kout` of lanes [c0, c0 + nvec) = (overwrite ? 0 : kout) + add * Q~ (vectors `kin`): kp_sums per lane, one
-    // pass over the tiles, kp_slab_reduce and kp_fin per lane (then_rr: and cg_rr, the reset's r.r of the new
+    // pass (pairs_multi), lane_raw and kp_fin per lane (then_rr: and cg_rr, the reset's r.r of the new
     // residual); flags: the lanes' stop flags apply
     void kp_lanes(int kin, int kout, int c0, int nvec, T add, bool overwrite, bool flags, bool then_rr = false);
     void cg_iter_multi(int nvec, int reset);
@@ -476,6 +491,10 @@ struct engine : engine_base {
     double otf_estimate_s(const int64_t *rowptr, const int32_t *col, const std::vector<int64_t> &colptr) const;
     void setup_otf(int rbf_fact_ok);
     void otf_dominant(const T *p, const cg_scalars<T> *status);
+    // the pair part of nvec vectors p + c * pstride in one pass, into raw_out + c * rstride; pk: [m][otf_lanes_nv(nvec)]
+    void otf_pairs_lanes(const T *p, int64_t pstride, T *raw_out, int64_t rstride, int nvec, T *pk, const cg_scalars<T> *status);
+    // L.raw += the separable part and the diagonal for p (through L.red; ssc: 2 device scalars of the lane's)
+    void otf_base(const cg_lane &L, T *ssc, const T *p, const cg_scalars<T> *status);
     void otf_kp_raw(const T *p, const cg_scalars<T> *status, bool with_base);
     bool sparse_stored() const { return sparse && !csr.dense_on; } // K·p through the CSR structures
     bool expansion_eligible();                                    // expand_setup.hip: K, coefficients; true if usable

@@ -8,22 +8,34 @@
 
 namespace plssvm_mi {
 
-// Where the finalize is kp_finalize_kernel / cg_fin_dad_kernel and nothing else: the pairwise tile path on one rank with
-// the reference recurrence. There G = 1, v0 = 0, vn = m, no collective, no centered finalize and no w pass riding with
-// the direction update, so the steps (kp_sums .. cg_dir) launch on a pool lane exactly what they launch for the single
-// solve there (need_pool). Held-out lanes are offered here, at any width.
+// Where the finalize is kp_finalize_kernel / cg_fin_dad_kernel and nothing else: one rank with the reference recurrence,
+// on the pairwise tile path or the sparse on-the-fly path. There G = 1, v0 = 0, vn = m, no collective, no centered
+// finalize and no w pass riding with the direction update, so the steps (kp_sums .. cg_dir) launch on a pool lane
+// exactly what they launch for the single solve there (need_pool).
+template <typename T>
+bool engine<T>::one_rank_reference() const {
+    return have_data && m > 0 && world == 1 && comm == nullptr && xchg == nullptr && sim_world == 0 && !shard && !cg1_wanted();
+}
+
+// The tile path: held-out lanes are offered here, at any width.
 template <typename T>
 bool engine<T>::held_supported() const {
     const bool tiles_path = !factored() && (!sparse || csr.dense_on);
-    return have_data && tiles_path && m > 0 && kp_wgs > 0 && world == 1 && comm == nullptr && xchg == nullptr &&
-           sim_world == 0 && !shard && !cg1_wanted();
+    return tiles_path && kp_wgs > 0 && one_rank_reference();
 }
 
-// The batched path: there, unless the width option says one at a time. Everything else runs the right-hand sides one
-// after another through the single-vector code.
+// The on-the-fly path: around its pair kernel the single product runs kp_sums, otf_base and the finalize, O(m) steps that
+// run per lane as they are (the stored sparse paths fill their LDS with one vector and stay one at a time).
+template <typename T>
+bool engine<T>::otf_lanes_ok() const {
+    return sparse && csr.otf_on && !csr.dense_on && !factored() && one_rank_reference();
+}
+
+// The batched path: on either, unless the width option says one at a time. Everything else runs the right-hand sides
+// one after another through the single-vector code.
 template <typename T>
 bool engine<T>::multi_batched() const {
-    return held_supported() && multi_opt != 1;
+    return (held_supported() || otf_lanes_ok()) && multi_opt != 1;
 }
 
 template <typename T>
@@ -35,7 +47,10 @@ void engine<T>::need_pool() {
 
 template <typename T>
 int64_t engine<T>::lane_bytes(bool with_sinv, bool with_hold) const {
-    return ((int64_t) (LV_COUNT + (with_sinv ? 1 : 0)) * q.size() + kp_wgs * KP_REC + 8 * RED_BLOCKS) * (int64_t) sizeof(T) +
+    // its slab on the tile path; on the on-the-fly path its column of the interleaved buffer (counted twice: the buffer
+    // is as wide as the next of 2, 4, 8 columns) and its two ssc scalars
+    const int64_t pass = otf_lanes_ok() ? 2 * m + 2 : kp_wgs * KP_REC;
+    return ((int64_t) (LV_COUNT + (with_sinv ? 1 : 0)) * q.size() + pass + 8 * RED_BLOCKS) * (int64_t) sizeof(T) +
            (int64_t) sizeof(cg_scalars<T>) + (with_hold ? q.size() : 0);
 }
 
@@ -61,9 +76,13 @@ int engine<T>::multi_lanes(bool with_sinv, bool with_hold) {
     for (int w = multi_width_next(with_sinv, with_hold); w >= 2; w /= 2) {
         try {
             lanes.vstride = q.size();
-            lanes.sstride = kp_wgs * KP_REC;
+            lanes.sstride = otf_lanes_ok() ? 0 : kp_wgs * KP_REC;
             lanes.vec.alloc((int64_t) LV_COUNT * w * lanes.vstride, stream);
             lanes.slab.alloc((int64_t) w * lanes.sstride, stream, false);
+            if (otf_lanes_ok()) {
+                lanes.pk.alloc(m * otf_lanes_nv(w), stream, false);
+                lanes.ssc.alloc(2 * w, stream);
+            }
             lanes.part.alloc((int64_t) w * 8 * RED_BLOCKS, stream);
             lanes.sc.alloc(w, stream);
             if (with_sinv) lanes.sinv.alloc((int64_t) w * lanes.vstride, stream);
@@ -118,30 +137,48 @@ void engine<T>::tiles_multi(int kind, int c0, int nvec, bool flags) {
                              lanes.sstride, nvec, flags ? lanes.sc.get() + c0 : nullptr, stream, kc.view());
 }
 
-// kp_device for lanes [c0, c0 + nvec) with one pass over the tiles (engine.hpp)
+// The one dispatch of the batched pass: over the tiles into the lanes' slabs, or over the pairs into the lanes' raw
+template <typename T>
+void engine<T>::pairs_multi(int kind, int c0, int nvec, bool flags) {
+    if (lanes.sstride > 0) {
+        tiles_multi(kind, c0, nvec, flags);
+        return;
+    }
+    otf_pairs_lanes(lane_v(kind, c0), lanes.vstride, lane_v(LV_RAW, c0), lanes.vstride, nvec, lanes.pk.get(),
+                    flags ? lanes.sc.get() + c0 : nullptr);
+}
+
+template <typename T>
+void engine<T>::lane_raw(int kind, int c, const cg_scalars<T> *status) {
+    const cg_lane L = pool_lane(c);
+    if (lanes.sstride > 0) kp_slab_reduce(L, status);
+    else otf_base(L, lane_ssc(c), lane_v(kind, c), status);
+}
+
+// kp_device for lanes [c0, c0 + nvec) with one pass over the tiles or the pairs (engine.hpp)
 template <typename T>
 void engine<T>::kp_lanes(int kin, int kout, int c0, int nvec, T add, bool overwrite, bool flags, bool then_rr) {
     for (int c = c0; c < c0 + nvec; ++c) {
         const cg_lane L = pool_lane(c);
         kp_sums(lane_v(kin, c), L, flags ? L.sc : nullptr);
     }
-    tiles_multi(kin, c0, nvec, flags);
+    pairs_multi(kin, c0, nvec, flags);
     for (int c = c0; c < c0 + nvec; ++c) {
         const cg_lane L = pool_lane(c);
         const cg_scalars<T> *st = flags ? L.sc : nullptr;
-        kp_slab_reduce(L, st);
+        lane_raw(kin, c, st);
         kp_fin(L, lane_v(kin, c), lane_v(kout, c), add, overwrite, st);
         if (then_rr) cg_rr(L, st);
     }
 }
 
-// cg_iter for nvec lanes: one batched tile launch on the direction vectors, then cg_iter's steps per lane
+// cg_iter for nvec lanes: one batched pass on the direction vectors, then cg_iter's steps per lane
 template <typename T>
 void engine<T>::cg_iter_multi(int nvec, int reset) {
-    tiles_multi(LV_D, 0, nvec, true);
+    pairs_multi(LV_D, 0, nvec, true);
     for (int c = 0; c < nvec; ++c) {
         const cg_lane L = pool_lane(c);
-        kp_slab_reduce(L, L.sc);
+        lane_raw(LV_D, c, L.sc);
         cg_fin_dad(L, L.d, L.pdad(), nullptr, 0);
         cg_upd_rr(L, reset);
     }
@@ -616,7 +653,7 @@ void engine<T>::train_values(const T *ALPHA, int64_t nclass, int64_t lda, const 
         OUT[c * ldo + m] = (acc + last) + (T) bias[c];
     }
     if (m <= 0) return;
-    const int W = nclass == 1 ? 1 : multi_lanes();
+    const int W = nclass == 1 || !held_supported() ? 1 : multi_lanes();  // batched over the tiles only
     if (W < 2) {  // one vector after another: kp_part's K·p, then the finalize
         for (int64_t c = 0; c < nclass; ++c) {
             const T *a = ALPHA + c * lda;
@@ -700,6 +737,10 @@ void engine<T>::time_kp_multi(int64_t nrhs, int reps, double *ms_kp) {
     template int engine<T>::multi_lanes(bool, bool);                                                                 \
     template void engine<T>::lanes_own_diag();                                                                       \
     template void engine<T>::tiles_multi(int, int, int, bool);                                                       \
+    template void engine<T>::pairs_multi(int, int, int, bool);                                                       \
+    template void engine<T>::lane_raw(int, int, const cg_scalars<T> *);                                              \
+    template bool engine<T>::one_rank_reference() const;                                                             \
+    template bool engine<T>::otf_lanes_ok() const;                                                                   \
     template void engine<T>::kp_lanes(int, int, int, int, T, bool, bool, bool);                                      \
     template void engine<T>::cg_iter_multi(int, int);                                                                \
     template void engine<T>::solve_cg_group(const T *, int, int64_t, int64_t, T, T *, double *, int64_t *, bool);    \

@@ -350,6 +350,157 @@ __global__ __launch_bounds__(OTF_NT) void otf_kp_kernel(const int64_t *__restric
     }
 }
 
+// ---- several vectors per pass over the pairs (engine.hpp "lanes") --------------------------------
+// s_ij and c_ij depend on neither the vector nor a lane's diagonal, and re-forming s_ij is what the path costs: the
+// lanes kernel walks each window once, evaluates otf_c once per pair and multiplies it into every lane's p_j.
+//
+// Partner data of the scan: (|x_j|^2, e_j) is the setup's (otf_ne, built once), the lanes' p_j come interleaved,
+// pk[j][NV], so one partner's NV values are one contiguous vector load (rebuilt per product by otf_pack_lanes_kernel).
+template <typename T>
+struct alignas(2 * sizeof(T)) otf_ne {
+    T n, e;
+};
+template <typename T, int NV>
+struct alignas(NV * sizeof(T)) otf_pv {
+    T p[NV];
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void otf_ne_kernel(const T *__restrict__ norms, const T *__restrict__ ev, int64_t m,
+                                                     otf_ne<T> *__restrict__ ne) {
+    const int64_t j = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < m) ne[j] = otf_ne<T>{ norms[j], ev != nullptr ? ev[j] : T(1) };
+}
+
+// bit c = vector c of nvec is still iterating (status null: all are)
+template <typename T>
+__device__ __forceinline__ unsigned otf_live(const cg_scalars<T> *__restrict__ status, int nvec) {
+    unsigned live = 0;
+    for (int c = 0; c < nvec; ++c)
+        if (status == nullptr || !status[c].converged) live |= 1u << c;
+    return live;
+}
+
+// pk[j][c] = p_c[j] for the nvec strided vectors p + c * pstride (coalesced reads per vector, one vector store per
+// partner); the columns past nvec are zero
+template <typename T, int NV>
+__global__ __launch_bounds__(256) void otf_pack_lanes_kernel(const T *__restrict__ p, int64_t pstride, int nvec, int64_t m,
+                                                             otf_pv<T, NV> *__restrict__ pk,
+                                                             const cg_scalars<T> *__restrict__ status) {
+    if (otf_live<T>(status, nvec) == 0) return;
+    const int64_t j = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    otf_pv<T, NV> v;
+#pragma unroll
+    for (int c = 0; c < NV; ++c) v.p[c] = c < nvec ? p[c * pstride + j] : T(0);
+    pk[j] = v;
+}
+
+// Scan steps whose partner loads are in flight together. A step holds s, (n, e) and NV values of p, 3 + NV values
+// against the single kernel's 5 (s and the 4-value pne record): the depth falls with NV so that every instance stays
+// within the single kernel's registers per wave — 96 (fp32, 5 waves per SIMD) and 168 (fp64, 3), no scratch.
+template <typename T, int NV>
+constexpr int otf_scan_lanes() {
+    return sizeof(T) == 4 ? (NV <= 2 ? 8 : 4) : (NV <= 4 ? 4 : 2);
+}
+
+// raw_c[i] = sum_{j != i, s_ij != 0} c_ij p_c[j] for the live vectors c < nvec (raw_c = raw + c * rstride), rows
+// [r0, r1), all windows in one launch. The walk is otf_kp_kernel's statement for statement (so is s_ij, bit for bit);
+// the scan visits the window in the same lane-strided order and adds (double) c_ij * (double) p_c[j] into one double
+// accumulator per vector, reduced by the same __shfl_xor tree: raw_c is bitwise what otf_kp_kernel writes for p_c. A
+// converged vector's raw is left alone; the kernel leaves when every vector has converged.
+template <typename T, int CWB, int NV>
+__global__ __launch_bounds__(OTF_NT) void otf_kp_lanes_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                                              const T *__restrict__ val, const int64_t *__restrict__ ecb,
+                                                              const otf_jv<T> *__restrict__ cjv, const int2 *__restrict__ seg,
+                                                              const T *__restrict__ norms, const T *__restrict__ ev,
+                                                              const otf_ne<T> *__restrict__ ne,
+                                                              const otf_pv<T, NV> *__restrict__ pk, int64_t m, int64_t nW,
+                                                              int64_t r0, int64_t r1, otf_pair<T> pf, int nvec,
+                                                              T *__restrict__ raw, int64_t rstride,
+                                                              const cg_scalars<T> *__restrict__ status) {
+    constexpr int CW = otf_cw<T, CWB>();
+    constexpr int SCAN = otf_scan_lanes<T, NV>();
+    static_assert(CW % (64 * SCAN) == 0, "the scan covers a window in whole groups of steps");
+    __shared__ T S[OTF_NT / 64][CW];
+    const unsigned live = otf_live<T>(status, nvec);
+    if (live == 0) return;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int64_t i = r0 + (int64_t) blockIdx.x * (OTF_NT / 64) + wave;
+    if (i >= r1) return;
+    T *s = S[wave];
+    for (int t = lane; t < CW; t += 64) s[t] = T(0);
+    const int64_t b0 = rowptr[i], nz = rowptr[i + 1] - b0;
+    const T ni = norms[i], ei = ev != nullptr ? ev[i] : T(1);
+    const bool h0 = lane < nz;
+    const int32_t f0 = h0 ? col[b0 + lane] : 0;
+    const T v0 = h0 ? val[b0 + lane] : T(0);
+    const int64_t c0 = h0 ? ecb[b0 + lane] : 0;
+    int2 sg0 = h0 ? seg[(int64_t) f0 * nW] : make_int2(0, 0);
+    double acc[NV];
+#pragma unroll
+    for (int c = 0; c < NV; ++c) acc[c] = 0.0;
+    for (int64_t W = 0; W < nW; ++W) {
+        const int j0 = (int) (W * CW);
+        if (nz > 0) {
+            const int2 sg = sg0;
+            sg0 = h0 && W + 1 < nW ? seg[(int64_t) f0 * nW + W + 1] : make_int2(0, 0);
+            if constexpr (OTF_V2) otf_batch2<T>(s, cjv, j0, (int) (nz < 64 ? nz : 64), c0 + sg.x, sg.y, v0, lane);
+            else otf_batch<T>(s, cjv, j0, (int) (nz < 64 ? nz : 64), c0 + sg.x, sg.y, v0, lane);
+        }
+        for (int64_t q0 = 64; q0 < nz; q0 += 64) {  // further features: reloaded per window
+            const int64_t k = q0 + lane;
+            int64_t lo = 0;
+            int len = 0;
+            T v = T(0);
+            if (k < nz) {
+                const int32_t f = col[b0 + k];
+                v = val[b0 + k];
+                const int2 sg = seg[(int64_t) f * nW + W];
+                lo = ecb[b0 + k] + sg.x;
+                len = sg.y;
+            }
+            if constexpr (OTF_V2) otf_batch2<T>(s, cjv, j0, (int) (nz - q0 < 64 ? nz - q0 : 64), lo, len, v, lane);
+            else otf_batch<T>(s, cjv, j0, (int) (nz - q0 < 64 ? nz - q0 : 64), lo, len, v, lane);
+        }
+        // the partners' (n_j, e_j) and NV values of p come unconditionally, SCAN steps ahead of their use, like the single
+        // kernel's record: loads that waited for s_ij != 0 would put an LDS read in front of every memory latency
+        for (int t0 = 0; t0 < CW; t0 += 64 * SCAN) {
+            T sv[SCAN];
+            otf_ne<T> q[SCAN];
+            otf_pv<T, NV> pv[SCAN];
+#pragma unroll
+            for (int u = 0; u < SCAN; ++u) {
+                const int t = t0 + 64 * u + lane;
+                sv[u] = s[t];
+                const int64_t j = j0 + t;
+                const int64_t jc = j < m ? j : m - 1;
+                q[u] = ne[jc];
+                pv[u] = pk[jc];
+            }
+#pragma unroll
+            for (int u = 0; u < SCAN; ++u) {
+                if (sv[u] != T(0)) {
+                    const int t = t0 + 64 * u + lane;
+                    s[t] = T(0);
+                    if (j0 + t != i) {
+                        const double c = (double) otf_c<T>(pf, sv[u], ni, q[u].n, ei, q[u].e);
+#pragma unroll
+                        for (int v = 0; v < NV; ++v) acc[v] += c * (double) pv[u].p[v];
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        double a = acc[v];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) a += __shfl_xor(a, off);
+        if (lane == 0 && ((live >> v) & 1u)) raw[v * rstride + i] = (T) a;
+    }
+}
+
 }  // namespace
 
 // device bytes and an estimated time (s) of one on-the-fly K·p share, from the host CSR / CSC counts
@@ -388,15 +539,22 @@ void engine<T>::setup_otf(int rbf_fact_ok) {
         hipLaunchKernelGGL(otf_ecb_kernel, dim3((unsigned) ceil_div(csr.nnz, 256)), dim3(256), 0, stream,
                            csr.colptr.get(), csr.col.get(), csr.nnz, csr.ecb.get());
     MI_LAUNCH_CHECK();
+    // the scan's per-partner (|x_j|^2, e_j) of the lanes kernel: the setup's, not a product's
+    csr.otf_ne.alloc(2 * std::max<int64_t>(m, 1), stream, false);
+    if (m > 0)
+        hipLaunchKernelGGL(otf_ne_kernel<T>, dim3((unsigned) ceil_div(m, 256)), dim3(256), 0, stream, norms.get(),
+                           kernel == 2 ? csr.e.get() : nullptr, m, reinterpret_cast<otf_ne<T> *>(csr.otf_ne.get()));
+    MI_LAUNCH_CHECK();
     if (csr.ssc.get() == nullptr) csr.ssc.alloc(1, stream);
     csr.rbf_factored = kernel == 2 && rbf_form != 1 && rbf_fact_ok;
     MI_HIP_CHECK(hipStreamSynchronize(stream));
     csr.otf_on = true;
 }
 
+namespace {
+// the pair part's form and constants for the engine's kernel function (both pair kernels)
 template <typename T>
-void engine<T>::otf_dominant(const T *p, const cg_scalars<T> *status) {
-    if (r1 <= r0) return;
+otf_pair<T> otf_pair_of(int kernel, int degree, T gamma, T coef0, bool rbf_factored) {
     otf_pair<T> pf{};
     pf.kernel = kernel;
     pf.deg = degree;
@@ -415,9 +573,17 @@ void engine<T>::otf_dominant(const T *p, const cg_scalars<T> *status) {
             }
         }
     } else {
-        pf.form = csr.rbf_factored ? 0 : 1;
+        pf.form = rbf_factored ? 0 : 1;
     }
     pf.kappa = kappa;
+    return pf;
+}
+}  // namespace
+
+template <typename T>
+void engine<T>::otf_dominant(const T *p, const cg_scalars<T> *status) {
+    if (r1 <= r0) return;
+    const otf_pair<T> pf = otf_pair_of<T>(kernel, degree, gamma, coef0, csr.rbf_factored);
     pne_t<T> *pne = reinterpret_cast<pne_t<T> *>(csr.pne.get());
     hipLaunchKernelGGL(otf_pack_kernel<T>, dim3((unsigned) ceil_div(m, 256)), dim3(256), 0, stream, p, norms.get(),
                        kernel == 2 ? csr.e.get() : nullptr, m, pne, status);
@@ -434,6 +600,52 @@ void engine<T>::otf_dominant(const T *p, const cg_scalars<T> *status) {
     MI_LAUNCH_CHECK();
 }
 
+// The pair part of nvec <= KP_MULTI_W vectors p + c * pstride in one pass over the pairs, into raw + c * rstride (every
+// row of [r0, r1) is written: no clearing first); status: the vectors' stop flags, status[c] (null: none). pk: the
+// interleaved [m][NV] buffer, NV = otf_lanes_nv(nvec) — the widths 2, 4 and 8 are instantiated, a narrower group runs in
+// the next one with its spare columns zero and never written.
+int otf_lanes_nv(int nvec) { return nvec <= 2 ? 2 : nvec <= 4 ? 4 : KP_MULTI_W; }
+
+template <typename T>
+void engine<T>::otf_pairs_lanes(const T *p, int64_t pstride, T *raw_out, int64_t rstride, int nvec, T *pk,
+                                const cg_scalars<T> *status) {
+    if (r1 <= r0) return;
+    if (nvec < 1 || nvec > KP_MULTI_W) throw mi_error(-1, "bad vector count for the batched on-the-fly kernel");
+    const otf_pair<T> pf = otf_pair_of<T>(kernel, degree, gamma, coef0, csr.rbf_factored);
+    auto launch = [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        otf_pv<T, NV> *pkv = reinterpret_cast<otf_pv<T, NV> *>(pk);
+        hipLaunchKernelGGL((otf_pack_lanes_kernel<T, NV>), dim3((unsigned) ceil_div(m, 256)), dim3(256), 0, stream, p, pstride,
+                           nvec, m, pkv, status);
+        MI_LAUNCH_CHECK();
+        hipLaunchKernelGGL((otf_kp_lanes_kernel<T, OTF_CWB, NV>), dim3((unsigned) ceil_div(r1 - r0, OTF_NT / 64)), dim3(OTF_NT),
+                           0, stream, csr.rowptr.get(), csr.col.get(), csr.val.get(), csr.ecb.get(),
+                           reinterpret_cast<const otf_jv<T> *>(csr.cjv.get()), csr.seg.get(), norms.get(),
+                           kernel == 2 ? csr.e.get() : nullptr, reinterpret_cast<const otf_ne<T> *>(csr.otf_ne.get()), pkv, m,
+                           csr.otf_nw, r0, r1, pf, nvec, raw_out, rstride, status);
+        MI_LAUNCH_CHECK();
+    };
+    switch (otf_lanes_nv(nvec)) {
+        case 2: launch(std::integral_constant<int, 2>{}); break;
+        case 4: launch(std::integral_constant<int, 4>{}); break;
+        default: launch(std::integral_constant<int, KP_MULTI_W>{}); break;
+    }
+}
+
+// raw += the separable part kappa_ij p_j and the diagonal, for the vector p of the lane L (the engine's own: ssc =
+// csr.ssc): sum e p (rbf) or sum p (poly) through L.red into ssc, then gram_base_kernel — O(m)
+template <typename T>
+void engine<T>::otf_base(const cg_lane &L, T *ssc, const T *p, const cg_scalars<T> *status) {
+    launch_dot2<T>(p, kernel == 2 ? csr.e.get() : nullptr, nullptr, nullptr, m, L.red, status, stream);
+    launch_dot_final<T>(L.red, L.sc, FIN_PLAIN, 0, nullptr, 0, ssc, stream);
+    T kappa = 0;
+    if (kernel == 1) {
+        kappa = 1;
+        for (int q2 = 0; q2 < degree; ++q2) kappa *= coef0;
+    }
+    launch_gram_base<T>(kernel, kf(), kappa, ssc, norms.get(), csr.e.get(), p, m, L.raw, status, stream);
+}
+
 // raw = sum_j k_ij p_j (with_base: + the separable part and the diagonal, as the Gram pattern's)
 template <typename T>
 void engine<T>::otf_kp_raw(const T *p, const cg_scalars<T> *status, bool with_base) {
@@ -441,22 +653,15 @@ void engine<T>::otf_kp_raw(const T *p, const cg_scalars<T> *status, bool with_ba
     gather_input(p);  // sharded group: the partners' p from every rank
     otf_dominant(p, status);
     if (!shard) allgather_rows(raw.get());
-    if (with_base && !(sim_world > 0 && sim_rank != 0)) {
-        launch_dot2<T>(p, kernel == 2 ? csr.e.get() : nullptr, nullptr, nullptr, m, red.get(), status, stream);
-        launch_dot_final<T>(red.get(), sc.get(), FIN_PLAIN, 0, nullptr, 0, csr.ssc.get(), stream);
-        T kappa = 0;
-        if (kernel == 1) {
-            kappa = 1;
-            for (int q2 = 0; q2 < degree; ++q2) kappa *= coef0;
-        }
-        launch_gram_base<T>(kernel, kf(), kappa, csr.ssc.get(), norms.get(), csr.e.get(), p, m, raw.get(), status, stream);
-    }
+    if (with_base && !(sim_world > 0 && sim_rank != 0)) otf_base(own_lane(), csr.ssc.get(), p, status);
 }
 
 #define INST(T)                                                                                                        \
     template double engine<T>::otf_estimate_s(const int64_t *, const int32_t *, const std::vector<int64_t> &) const;   \
     template void engine<T>::setup_otf(int);                                                                           \
     template void engine<T>::otf_dominant(const T *, const cg_scalars<T> *);                                           \
+    template void engine<T>::otf_pairs_lanes(const T *, int64_t, T *, int64_t, int, T *, const cg_scalars<T> *);      \
+    template void engine<T>::otf_base(const cg_lane &, T *, const T *, const cg_scalars<T> *);                         \
     template void engine<T>::otf_kp_raw(const T *, const cg_scalars<T> *, bool);
 INST(float)
 INST(double)

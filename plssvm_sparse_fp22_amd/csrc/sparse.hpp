@@ -138,6 +138,7 @@ struct csr_data {
     dev_buf<T> pne;         // [m][4]: p_j, |x_j|^2, e_j, 0 of the current K·p
     dev_buf<T> cjv;         // [nnz][2]: CSC (row, value) pairs (the row as int32 bits in the first slot)
     dev_buf<double> otf_part;  // [m]: row sums of the windows done so far (K·p split over launches)
+    dev_buf<T> otf_ne;      // [m][2]: |x_j|^2, e_j (1 off the rbf kernel) — the lanes kernel's per-partner record
 
     vals_t<T> rvals() const { return vals_t<T>{ val.get(), nullptr }; }
     vals_t<T> cvals() const { return vals_t<T>{ cval.get(), nullptr }; }
@@ -145,9 +146,12 @@ struct csr_data {
         return rowptr.bytes() + col.bytes() + val.bytes() + colptr.bytes() + crow.bytes() +
                cval.bytes() + spmv_csc.bytes() + spmv_csr.bytes() + rb_csr.bytes() + e.bytes() + pj.bytes() + ps.bytes() +
                rb_base.bytes() + rowoff.bytes() + cells.bytes() + slab_row.bytes() + slab_col.bytes() + cbnd.bytes() + ex.bytes() +
-               seg.bytes() + ecb.bytes() + pne.bytes() + cjv.bytes() + otf_part.bytes();
+               seg.bytes() + ecb.bytes() + pne.bytes() + cjv.bytes() + otf_part.bytes() + otf_ne.bytes();
     }
 };
+
+// the interleaved width (2, 4 or KP_MULTI_W) in which the on-the-fly lanes kernel runs nvec vectors (otf.hip)
+int otf_lanes_nv(int nvec);
 
 // raw_i += the separable part of sum_j k_ij p_j and the diagonal pair (sparse.hip; Gram pattern and
 // on-the-fly paths, after the group exchange)
