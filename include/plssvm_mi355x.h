@@ -367,10 +367,14 @@ PLSSVM_MI_API int plssvm_mi_train_values(plssvm_mi_ctx *ctx, const void *ALPHA, 
  * weights apply to every lane. Lane l is BITWISE the same call on a fresh context created with gamma = gammas[l] on the
  * same data, whatever nlane, the lane's position or that context's tile cache. More lanes than the width
  * (plssvm_mi_info.multi_width) run in groups, in order.
- * Offered for dense data (plssvm_mi_setup_dense) with PLSSVM_MI_KERNEL_RBF or _LAPLACIAN on one GPU where the lanes are
- * batched (the reference CG, PLSSVM_MI_OPT_MULTI_WIDTH != 1). Sparse data, the linear or polynomial kernel, a group, a
- * simulated rank, the one-reduction CG: PLSSVM_MI_ERR_UNSUPPORTED, plssvm_mi_last_error names the reason, the context
- * stays usable. No room for two lanes: PLSSVM_MI_ERR_OOM. nlane < 1, a gamma (or cost) that is not finite and > 0, a
+ * Offered for dense data (plssvm_mi_setup_dense) with PLSSVM_MI_KERNEL_RBF or _LAPLACIAN, and for sparse data on the
+ * on-the-fly path (plssvm_mi_setup_csr / _coo with PLSSVM_MI_SPARSE_ONTHEFLY, chosen or set) with PLSSVM_MI_KERNEL_RBF,
+ * on one GPU where the lanes are batched (the reference CG, PLSSVM_MI_OPT_MULTI_WIDTH != 1). On the on-the-fly path no
+ * gamma enters the walk that re-forms x_i . x_j: a group of lanes makes one walk per product, and each lane evaluates its
+ * own pair values (in the form, factored or direct, that a fresh context with its gamma chooses) from its own
+ * exp(-gamma_l |x|^2) vectors, built once per group. Sparse data on a stored path (kernel expansion, Gram pattern) or
+ * densified, the linear or polynomial kernel, a group, a simulated rank, the one-reduction CG:
+ * PLSSVM_MI_ERR_UNSUPPORTED, plssvm_mi_last_error names the reason ("gamma lanes run on ..."), the context stays usable. No room for two lanes: PLSSVM_MI_ERR_OOM. nlane < 1, a gamma (or cost) that is not finite and > 0, a
  * too small ld: PLSSVM_MI_ERR_ARG.
  *
  * plssvm_mi_kp_gammas: RET_l += add * Q~_{gamma_l} P_l for l < nlane (rows ld >= m apart), each row as plssvm_mi_kp

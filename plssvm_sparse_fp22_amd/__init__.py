@@ -585,9 +585,10 @@ class CSVM:
         return np.ascontiguousarray(g)
 
     def run_device_kernel_gammas(self, gammas, RET, P, add):
-        """RET[l] += add * Q~(gammas[l]) P[l] for the rbf or laplacian kernel on dense data: one pass over the tiles forms
-        every pair's distance once for all lanes. Row l is bitwise run_device_kernel (q=None, after generate_q) of a fresh
-        context with gamma = gammas[l]; this context's gamma, q and stored tiles are untouched."""
+        """RET[l] += add * Q~(gammas[l]) P[l] for the rbf or laplacian kernel on dense data (one pass over the tiles forms
+        every pair's distance once for all lanes) and for the rbf kernel on sparse data on the on-the-fly path (one walk
+        over the pairs forms every x_i . x_j once for all lanes). Row l is bitwise run_device_kernel (q=None, after
+        generate_q) of a fresh context with gamma = gammas[l]; this context's gamma, q and stored tiles are untouched."""
         g = self._gammas(gammas)
         assert RET.dtype == self.dtype and RET.flags.c_contiguous and RET.ndim == 2
         PP = _rows(P, self.dtype, self.m, "P")
@@ -602,7 +603,8 @@ class CSVM:
         """learn() at every (gammas[k], costs[k]) (costs None: the context's cost on every lane; a (C, gamma) grid is the
         caller's product of the two axes), as lanes of one batched CG whose K.p forms each pair's distance once for all
         lanes. Row k of alphas [K][n], biases [K], iters_multi, traces is bitwise set_cost(costs[k]); learn() of a fresh
-        context with gamma = gammas[k]. Sets gammas (and costs); the context's own gamma, cost and q stay."""
+        context with gamma = gammas[k]. Dense data (rbf, laplacian) or sparse data on the on-the-fly path (rbf); other
+        setups raise BackendError with the reason. Sets gammas (and costs); the context's own gamma, cost and q stay."""
         if self.params.labels is None:
             raise ValueError("No labels given for training! Maybe the data is only usable for prediction?")
         g = self._gammas(gammas)

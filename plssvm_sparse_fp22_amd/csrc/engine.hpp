@@ -274,6 +274,7 @@ struct engine : engine_base {
         double *trace;
         int64_t trace_cap;
         const T *q = nullptr;  // the lane's own q (a gamma lane); null: the engine's qf()
+        const T *e = nullptr;  // a gamma lane's own e_i = exp(-gamma_l |x_i|^2) on the on-the-fly path; null: csr.e
         T *pdad() const { return cgp + 2 * RED_BLOCKS; }
         T *prr() const { return cgp + 4 * RED_BLOCKS; }
     };
@@ -286,7 +287,7 @@ struct engine : engine_base {
         return { dg.cost_inv, dg.QA, dg.sinv, dg.hold, lane_v(LV_X, c), lane_v(LV_R, c), lane_v(LV_D, c), lane_v(LV_AD, c),
                  lane_v(LV_B, c), lane_v(LV_RAW, c), lane_cgp(c), lane_red(c),
                  lanes.slab.get() + (int64_t) c * lanes.sstride, lanes.sc.get() + c,
-                 lanes.trace.get() + (int64_t) c * lanes.trace_cap, lanes.trace_cap, dg.q };
+                 lanes.trace.get() + (int64_t) c * lanes.trace_cap, lanes.trace_cap, dg.q, dg.e };
     }
     const T *lane_qf(const cg_lane &L) const { return L.q != nullptr ? L.q : qf(); }  // the q the lane's steps read
     // The steps take the rows [v0, v0 + vn), sum the G ranks' partials (gather_partials) and use qf() / QAf() /
@@ -343,6 +344,7 @@ struct engine : engine_base {
         const T *sinv;
         const uint8_t *hold;
         const T *q = nullptr;  // a gamma lane's own q_i = k_gamma(x_i, x_m) (lane_pool::q); null: the engine's
+        const T *e = nullptr;  // a gamma lane's own e (lane_pool::ge, on-the-fly path); null: the engine's csr.e
     };
     struct lane_pool {
         // every lane's diagonal (cg_lane), set by the batched entry points before they run a group: the engine's own
@@ -354,7 +356,11 @@ struct engine : engine_base {
                                            // call that passes them (need_lane_buf)
         dev_buf<T> q;                      // [width][vstride] per-lane q: allocated by the first gamma-lane call
         std::vector<T> gam;                // the running gamma group's gamma per lane; empty: the lanes share the
-                                           // engine's kernel values (tiles_multi picks the tile launch by it)
+                                           // engine's kernel values (tiles_multi / pairs_multi pick the launch by it)
+        // gamma lanes on the on-the-fly path, allocated by the first gamma-lane call there
+        dev_buf<T> ge;                     // [width][vstride] per-lane e_i = exp(-gamma_l |x_i|^2) (otf_base)
+        dev_buf<T> gek;                    // the group's e interleaved for the scan, [m][otf_lanes_nv(width)]
+        std::vector<int> gform;            // the running group's pair form per lane: 0 factored, 1 direct
         int width = 0;                     // lanes allocated: 0 = not yet, 1 = none fit (one at a time)
         int64_t vstride = 0, sstride = 0;  // elements between two lanes' vectors / slabs
         dev_buf<T> vec;                    // [LV_COUNT][width][vstride], zero padded like the engine's vectors
@@ -367,7 +373,7 @@ struct engine : engine_base {
         int64_t trace_cap = 0;
         int64_t bytes() const {
             return vec.bytes() + slab.bytes() + pk.bytes() + ssc.bytes() + part.bytes() + sc.bytes() + trace.bytes() + sinv.bytes() +
-                   hold.bytes() + q.bytes();
+                   hold.bytes() + q.bytes() + ge.bytes() + gek.bytes();
         }
     };
     enum lane_vec { LV_X = 0, LV_R, LV_D, LV_AD, LV_B, LV_RAW, LV_COUNT };
@@ -384,17 +390,20 @@ struct engine : engine_base {
     bool otf_lanes_ok() const;
     bool multi_batched() const;
     // device memory of one lane (with_sinv: and its weight vector; with_hold: and its held-row flags)
-    int64_t lane_bytes(bool with_sinv = false, bool with_hold = false) const;
+    // with_gamma: and a gamma lane's q, on the on-the-fly path also its e and its column of the interleaved e
+    int64_t lane_bytes(bool with_sinv = false, bool with_hold = false, bool with_gamma = false) const;
     // the width the next multi call would use (1: one at a time); allocates nothing
-    int multi_width_next(bool with_sinv = false, bool with_hold = false) const;
+    int multi_width_next(bool with_sinv = false, bool with_hold = false, bool with_gamma = false) const;
     // the lanes, allocated at the first call (width halved until it fits)
-    int multi_lanes(bool with_sinv = false, bool with_hold = false);
-    // a per-lane buffer (lanes.sinv, lanes.hold) of an allocated pool, allocated on first need; false: no room for it
+    int multi_lanes(bool with_sinv = false, bool with_hold = false, bool with_gamma = false);
+    // a per-lane buffer (lanes.sinv, lanes.hold, lanes.q, lanes.ge) of an allocated pool, allocated on first need (count:
+    // its elements, 0 = width * vstride); false: no room for it
     template <typename U>
-    bool need_lane_buf(dev_buf<U> &buf);
+    bool need_lane_buf(dev_buf<U> &buf, int64_t count = 0);
     T *lane_sinv(int c) const { return lanes.sinv.get() + (int64_t) c * lanes.vstride; }
     uint8_t *lane_hold(int c) const { return lanes.hold.get() + (int64_t) c * lanes.vstride; }
     T *lane_q(int c) const { return lanes.q.get() + (int64_t) c * lanes.vstride; }
+    T *lane_ge(int c) const { return lanes.ge.get() + (int64_t) c * lanes.vstride; }
     T *lane_ssc(int c) const { return lanes.ssc.get() + 2 * c; }
     // The batched launch streams filled records only: if the tile cache is allocated and unfilled, `product` (a K·p of
     // the caller's choice on the single path, after sc is zeroed) fills it; true if it ran
@@ -468,7 +477,9 @@ struct engine : engine_base {
     // for the whole group and never stored; its q (lane_pool::q, one pass over X per group) and QA = k_mm + diag_m are its
     // own. The steps are the pool lanes' (the context's point weights apply to every lane), so lane l is bitwise a fresh
     // context with gamma_l. Dense data with the rbf or laplacian kernel where the lanes are batched (multi_batched() and
-    // room for the pool): everything else is ERR_UNSUPPORTED with the reason. Neither call moves the engine's gamma,
+    // room for the pool), and sparse data with the rbf kernel on the on-the-fly path (otf_lanes_ok()), where no gamma
+    // enters the walk that forms s_ij: one walk per product, lane l's pair values from its own gamma, form and e
+    // (otf_kp_gammas_kernel). Everything else is ERR_UNSUPPORTED with the reason. Neither call moves the engine's gamma,
     // cost, q, QA_cost or tile cache. K > width: groups of the width, in order.
     int gamma_pool();                                        // the checks; the pool with its q buffer; returns the width
     void gamma_group(const double *gammas, const T *costs, int nvec);  // lanes.gam, the lanes' q and diag for one group
@@ -479,6 +490,7 @@ struct engine : engine_base {
 
     // sparse paths (sparse.hip)
     void sparse_q();                                              // q, norms, e on CSR data
+    void sparse_gamma_eq(T g, T *e_out, T *q_out);                // e and q of a context with the rbf width g (m values each)
     void build_gram_blocks(const int64_t *cpos, int64_t max_inc);  // sparse Gram pattern (pairwise kernels)
     int64_t mem_budget() const;  // device bytes for stored per-pair structures (sparse paths, dense tile cache)
     // row_stats (optional): the sampled rows' partners sharing >= 2 features, mean and max
@@ -495,6 +507,10 @@ struct engine : engine_base {
     void otf_pairs_lanes(const T *p, int64_t pstride, T *raw_out, int64_t rstride, int nvec, T *pk, const cg_scalars<T> *status);
     // L.raw += the separable part and the diagonal for p (through L.red; ssc: 2 device scalars of the lane's)
     void otf_base(const cg_lane &L, T *ssc, const T *p, const cg_scalars<T> *status);
+    // gamma lanes on this path: the running group's forms, per-lane e and q and the interleaved e (once per group); the
+    // pair part of its nvec vectors in one pass, lane l at lanes.gam[l]
+    void otf_gamma_group();
+    void otf_pairs_gammas(const T *p, int64_t pstride, T *raw_out, int64_t rstride, int nvec, T *pk, const cg_scalars<T> *status);
     void otf_kp_raw(const T *p, const cg_scalars<T> *status, bool with_base);
     bool sparse_stored() const { return sparse && !csr.dense_on; } // K·p through the CSR structures
     bool expansion_eligible();                                    // expand_setup.hip: K, coefficients; true if usable

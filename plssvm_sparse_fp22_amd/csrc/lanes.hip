@@ -46,18 +46,20 @@ void engine<T>::need_pool() {
 }
 
 template <typename T>
-int64_t engine<T>::lane_bytes(bool with_sinv, bool with_hold) const {
+int64_t engine<T>::lane_bytes(bool with_sinv, bool with_hold, bool with_gamma) const {
     // its slab on the tile path; on the on-the-fly path its column of the interleaved buffer (counted twice: the buffer
     // is as wide as the next of 2, 4, 8 columns) and its two ssc scalars
     const int64_t pass = otf_lanes_ok() ? 2 * m + 2 : kp_wgs * KP_REC;
-    return ((int64_t) (LV_COUNT + (with_sinv ? 1 : 0)) * q.size() + pass + 8 * RED_BLOCKS) * (int64_t) sizeof(T) +
+    // a gamma lane: its q; on the on-the-fly path also its e and its column of the interleaved e (counted twice, as above)
+    const int64_t gam = with_gamma ? q.size() + (otf_lanes_ok() ? q.size() + 2 * m : 0) : 0;
+    return ((int64_t) (LV_COUNT + (with_sinv ? 1 : 0)) * q.size() + pass + gam + 8 * RED_BLOCKS) * (int64_t) sizeof(T) +
            (int64_t) sizeof(cg_scalars<T>) + (with_hold ? q.size() : 0);
 }
 
 // Lanes are taken from what the setup (tile cache included) left free, keeping 256 MiB for the single path's own
 // later needs (traces, a captured block): the widest of W, W / 2, ... that fits; 1 = not even two lanes fit.
 template <typename T>
-int engine<T>::multi_width_next(bool with_sinv, bool with_hold) const {
+int engine<T>::multi_width_next(bool with_sinv, bool with_hold, bool with_gamma) const {
     if (!multi_batched()) return 1;
     if (lanes.width > 0) return lanes.width;
     size_t free_b = 0, total_b = 0;
@@ -65,15 +67,15 @@ int engine<T>::multi_width_next(bool with_sinv, bool with_hold) const {
     MI_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
     const int64_t room = (int64_t) free_b - ((int64_t) 256 << 20);
     int w = multi_opt >= 2 ? std::min(multi_opt, KP_MULTI_W) : KP_MULTI_W;
-    while (w >= 2 && (int64_t) w * lane_bytes(with_sinv, with_hold) > room) w /= 2;
+    while (w >= 2 && (int64_t) w * lane_bytes(with_sinv, with_hold, with_gamma) > room) w /= 2;
     return std::max(w, 1);
 }
 
 template <typename T>
-int engine<T>::multi_lanes(bool with_sinv, bool with_hold) {
+int engine<T>::multi_lanes(bool with_sinv, bool with_hold, bool with_gamma) {
     if (!multi_batched()) return 1;
     if (lanes.width > 0) return lanes.width;
-    for (int w = multi_width_next(with_sinv, with_hold); w >= 2; w /= 2) {
+    for (int w = multi_width_next(with_sinv, with_hold, with_gamma); w >= 2; w /= 2) {
         try {
             lanes.vstride = q.size();
             lanes.sstride = otf_lanes_ok() ? 0 : kp_wgs * KP_REC;
@@ -104,11 +106,12 @@ int engine<T>::multi_lanes(bool with_sinv, bool with_hold) {
 // weights / hold rows). No room: the caller runs its lanes one after another.
 template <typename T>
 template <typename U>
-bool engine<T>::need_lane_buf(dev_buf<U> &buf) {
+bool engine<T>::need_lane_buf(dev_buf<U> &buf, int64_t count) {
     if (lanes.width < 2) return false;
-    if (buf.size() >= (int64_t) lanes.width * lanes.vstride) return true;
+    if (count <= 0) count = (int64_t) lanes.width * lanes.vstride;
+    if (buf.size() >= count) return true;
     try {
-        buf.alloc((int64_t) lanes.width * lanes.vstride, stream);
+        buf.alloc(count, stream);
     } catch (const mi_error &e) {
         if (e.code != -4) throw;
         (void) hipGetLastError();
@@ -144,8 +147,13 @@ void engine<T>::pairs_multi(int kind, int c0, int nvec, bool flags) {
         tiles_multi(kind, c0, nvec, flags);
         return;
     }
-    otf_pairs_lanes(lane_v(kind, c0), lanes.vstride, lane_v(LV_RAW, c0), lanes.vstride, nvec, lanes.pk.get(),
-                    flags ? lanes.sc.get() + c0 : nullptr);
+    const cg_scalars<T> *status = flags ? lanes.sc.get() + c0 : nullptr;
+    if (!lanes.gam.empty()) {  // gamma lanes: the running group, lanes 0 .. nvec - 1, each under its own width
+        if (c0 != 0) throw mi_error(-6, "a group of gamma lanes starts at lane 0");
+        otf_pairs_gammas(lane_v(kind, 0), lanes.vstride, lane_v(LV_RAW, 0), lanes.vstride, nvec, lanes.pk.get(), status);
+        return;
+    }
+    otf_pairs_lanes(lane_v(kind, c0), lanes.vstride, lane_v(LV_RAW, c0), lanes.vstride, nvec, lanes.pk.get(), status);
 }
 
 template <typename T>
@@ -497,19 +505,24 @@ template <typename T>
 int engine<T>::gamma_pool() {
     need_data();
     const char *why = (kernel != 2 && kernel != KF_LAPLACIAN) ? "a kernel without a distance that all gammas share (linear, polynomial)"
-                      : sparse                                ? "sparse (CSR) data"
+                      : (sparse && csr.dense_on)              ? "sparse (CSR) data densified on the device"
+                      : (sparse && !csr.otf_on)               ? "sparse (CSR) data on a stored path (kernel expansion, Gram pattern)"
                       : (sim_world > 0)                       ? "a simulated rank"
                       : (world > 1 || comm != nullptr || xchg != nullptr || shard) ? "a multi-GPU group"
                       : cg1_wanted()                          ? "the one-reduction CG"
-                      : !held_supported()                     ? "a setup without kernel-matrix tiles"
+                      : !(held_supported() || otf_lanes_ok()) ? "a setup without kernel-matrix tiles"
                       : multi_opt == 1                        ? "set to one vector at a time (PLSSVM_MI_OPT_MULTI_WIDTH = 1)"
                                                               : nullptr;
     if (why != nullptr)
-        throw mi_error(-5, std::string("gamma lanes run on dense data with the rbf or laplacian kernel, on one GPU with the "
-                                       "batched reference CG; this context is ") + why + " (use one context per gamma instead)");
+        throw mi_error(-5, std::string("gamma lanes run on dense data with the rbf or laplacian kernel, and on sparse data on "
+                                       "the on-the-fly path with the rbf kernel, on one GPU with the batched reference CG; "
+                                       "this context is ") + why + " (use one context per gamma instead)");
     MI_HIP_CHECK(hipSetDevice(device));
-    const int W = multi_lanes();
-    if (W < 2 || !need_lane_buf(lanes.q)) throw mi_error(-4, "no device memory for two gamma lanes (use one context per gamma instead)");
+    const int W = multi_lanes(false, false, true);
+    // on the on-the-fly path a lane also has its e, and the group the interleaved copy of them
+    const bool room = W >= 2 && need_lane_buf(lanes.q) &&
+                      (!otf_lanes_ok() || (need_lane_buf(lanes.ge) && need_lane_buf(lanes.gek, std::max<int64_t>(m, 1) * otf_lanes_nv(W))));
+    if (!room) throw mi_error(-4, "no device memory for two gamma lanes (use one context per gamma instead)");
     need_pool();
     return W;
 }
@@ -517,11 +530,13 @@ int engine<T>::gamma_pool() {
 template <typename T>
 void engine<T>::gamma_group(const double *gammas, const T *costs, int nvec) {
     lanes.gam.assign(gammas, gammas + nvec);  // rounded to T as plssvm_mi_create rounds a context's gamma
-    launch_q_gammas<T>(kernel, lanes.gam.data(), nvec, XT.get(), n_pad, d, m, xlast.get(), lanes.q.get(), lanes.vstride, stream);
+    const bool otf = otf_lanes_ok();  // sparse data: the lanes' q from the CSR rows, and their own e
+    if (otf) otf_gamma_group();
+    else launch_q_gammas<T>(kernel, lanes.gam.data(), nvec, XT.get(), n_pad, d, m, xlast.get(), lanes.q.get(), lanes.vstride, stream);
     for (int c = 0; c < nvec; ++c) {
         const T cl = costs != nullptr ? costs[c] : cost;
         lanes.diag[(size_t) c] = lane_diag{ T(1) / cl, lane_QA(k_mm_at(lanes.gam[(size_t) c]), cl, weighted() ? sinv_h.data() : nullptr, m),
-                                            sinv_dev(), nullptr, lane_q(c) };
+                                            sinv_dev(), nullptr, lane_q(c), otf ? lane_ge(c) : nullptr };
     }
 }
 
@@ -733,8 +748,8 @@ void engine<T>::time_kp_multi(int64_t nrhs, int reps, double *ms_kp) {
 // every member defined in this file (need_lane_buf, a member template, is instantiated by its uses here)
 #define INST(T)                                                                                                      \
     template void engine<T>::need_pool();                                                                            \
-    template int64_t engine<T>::lane_bytes(bool, bool) const;                                                        \
-    template int engine<T>::multi_lanes(bool, bool);                                                                 \
+    template int64_t engine<T>::lane_bytes(bool, bool, bool) const;                                                  \
+    template int engine<T>::multi_lanes(bool, bool, bool);                                                               \
     template void engine<T>::lanes_own_diag();                                                                       \
     template void engine<T>::tiles_multi(int, int, int, bool);                                                       \
     template void engine<T>::pairs_multi(int, int, int, bool);                                                       \
@@ -746,7 +761,7 @@ void engine<T>::time_kp_multi(int64_t nrhs, int reps, double *ms_kp) {
     template void engine<T>::solve_cg_group(const T *, int, int64_t, int64_t, T, T *, double *, int64_t *, bool);    \
     template bool engine<T>::held_supported() const;                                                                 \
     template bool engine<T>::multi_batched() const;                                                                  \
-    template int engine<T>::multi_width_next(bool, bool) const;                                                      \
+    template int engine<T>::multi_width_next(bool, bool, bool) const;                                                    \
     template void engine<T>::solve_cg_multi(const T *, int64_t, int64_t, const T *, int64_t, T, T *, double *, int64_t *); \
     template void engine<T>::kp_multi(const T *, const T *, T *, int64_t, int64_t, T);                               \
     template void engine<T>::set_sinv(const std::vector<T> &);                                                       \

@@ -501,6 +501,135 @@ __global__ __launch_bounds__(OTF_NT) void otf_kp_lanes_kernel(const int64_t *__r
     }
 }
 
+// ---- several rbf widths per pass over the pairs (engine.hpp "gamma lanes") ------------------------
+// No gamma enters the walk: s_ij, |x_i|^2 and |x_j|^2 are the data's. A gamma lane (gamma_l, p_l) differs from the next
+// in the pair value c_ij^(l) only, so the gammas kernel walks each window once and evaluates otf_c's rbf expressions NV
+// times per non-zero s_ij, each lane with its own gamma, form and e^(l) = exp(-gamma_l |x|^2).
+//
+// Per-lane constants, by value (wave-uniform: they stay in scalar registers): gamma_l and the lane's form, 0 factored
+// e_i e_j expm1(2 g s), 1 direct exp(-g dist) - e_i e_j — the form a fresh context with gamma_l would choose, so the lanes
+// of one group may differ in it.
+template <typename T, int NV>
+struct otf_gam {
+    T g[NV];
+    int form[NV];
+};
+
+// Scan steps whose partner loads are in flight together. A step holds s, n_j, NV values of e_j and NV values of p,
+// 2 + 2 NV values against the lanes kernel's 3 + NV, and the pair's NV exponentials need their temporaries beside the NV
+// double accumulators: the depth is the largest at which the instance stays within the single kernel's registers per wave
+// (96 fp32, 168 fp64) without scratch (DESIGN.md §5.4.2 has the table).
+template <typename T, int NV>
+constexpr int otf_scan_gammas() {
+    return sizeof(T) == 4 ? (NV <= 2 ? 8 : NV <= 4 ? 4 : 1) : (NV <= 2 ? 4 : NV <= 4 ? 2 : 1);
+}
+
+// raw_l[i] = sum_{j != i, s_ij != 0} c_ij^(l) p_l[j] for the live lanes l < nvec, rows [r0, r1), all windows in one launch.
+// The walk is otf_kp_kernel's statement for statement (s_ij has its bits); the scan visits the window in the same
+// lane-strided order. The clamped distance does not depend on gamma and is formed once per pair; everything after it is
+// otf_c's expression at gamma_l on the lane's own e_i^(l), e_j^(l) (ek: the lanes' e interleaved like pk, one vector load
+// per partner; row i's NV values are wave-uniform), multiplied into p_l[j] in double and added to the lane's own
+// accumulator, reduced by the same __shfl_xor tree: raw_l is bitwise what otf_kp_kernel writes on a context with gamma_l.
+// A converged lane costs no exponential and its raw is left alone; the kernel leaves when every lane has converged.
+template <typename T, int CWB, int NV>
+__global__ __launch_bounds__(OTF_NT) void otf_kp_gammas_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                                               const T *__restrict__ val, const int64_t *__restrict__ ecb,
+                                                               const otf_jv<T> *__restrict__ cjv, const int2 *__restrict__ seg,
+                                                               const otf_ne<T> *__restrict__ ne,
+                                                               const otf_pv<T, NV> *__restrict__ ek,
+                                                               const otf_pv<T, NV> *__restrict__ pk, int64_t m, int64_t nW,
+                                                               int64_t r0, int64_t r1, otf_gam<T, NV> gm, int nvec,
+                                                               T *__restrict__ raw, int64_t rstride,
+                                                               const cg_scalars<T> *__restrict__ status) {
+    constexpr int CW = otf_cw<T, CWB>();
+    constexpr int SCAN = otf_scan_gammas<T, NV>();
+    static_assert(CW % (64 * SCAN) == 0, "the scan covers a window in whole groups of steps");
+    __shared__ T S[OTF_NT / 64][CW];
+    const unsigned live = otf_live<T>(status, nvec);
+    if (live == 0) return;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int64_t i = r0 + (int64_t) blockIdx.x * (OTF_NT / 64) + wave;
+    if (i >= r1) return;
+    T *s = S[wave];
+    for (int t = lane; t < CW; t += 64) s[t] = T(0);
+    const int64_t b0 = rowptr[i], nz = rowptr[i + 1] - b0;
+    const T ni = ne[i].n;
+    const otf_pv<T, NV> ei = ek[i];
+    const bool h0 = lane < nz;
+    const int32_t f0 = h0 ? col[b0 + lane] : 0;
+    const T v0 = h0 ? val[b0 + lane] : T(0);
+    const int64_t c0 = h0 ? ecb[b0 + lane] : 0;
+    int2 sg0 = h0 ? seg[(int64_t) f0 * nW] : make_int2(0, 0);
+    double acc[NV];
+#pragma unroll
+    for (int c = 0; c < NV; ++c) acc[c] = 0.0;
+    for (int64_t W = 0; W < nW; ++W) {
+        const int j0 = (int) (W * CW);
+        if (nz > 0) {
+            const int2 sg = sg0;
+            sg0 = h0 && W + 1 < nW ? seg[(int64_t) f0 * nW + W + 1] : make_int2(0, 0);
+            if constexpr (OTF_V2) otf_batch2<T>(s, cjv, j0, (int) (nz < 64 ? nz : 64), c0 + sg.x, sg.y, v0, lane);
+            else otf_batch<T>(s, cjv, j0, (int) (nz < 64 ? nz : 64), c0 + sg.x, sg.y, v0, lane);
+        }
+        for (int64_t q0 = 64; q0 < nz; q0 += 64) {  // further features: reloaded per window
+            const int64_t k = q0 + lane;
+            int64_t lo = 0;
+            int len = 0;
+            T v = T(0);
+            if (k < nz) {
+                const int32_t f = col[b0 + k];
+                v = val[b0 + k];
+                const int2 sg = seg[(int64_t) f * nW + W];
+                lo = ecb[b0 + k] + sg.x;
+                len = sg.y;
+            }
+            if constexpr (OTF_V2) otf_batch2<T>(s, cjv, j0, (int) (nz - q0 < 64 ? nz - q0 : 64), lo, len, v, lane);
+            else otf_batch<T>(s, cjv, j0, (int) (nz - q0 < 64 ? nz - q0 : 64), lo, len, v, lane);
+        }
+        // the partners' n_j and the NV values of e_j and of p come unconditionally, SCAN steps ahead of their use
+        for (int t0 = 0; t0 < CW; t0 += 64 * SCAN) {
+            T sv[SCAN], nj[SCAN];
+            otf_pv<T, NV> ej[SCAN], pv[SCAN];
+#pragma unroll
+            for (int u = 0; u < SCAN; ++u) {
+                const int t = t0 + 64 * u + lane;
+                sv[u] = s[t];
+                const int64_t j = j0 + t;
+                const int64_t jc = j < m ? j : m - 1;
+                nj[u] = ne[jc].n;
+                ej[u] = ek[jc];
+                pv[u] = pk[jc];
+            }
+#pragma unroll
+            for (int u = 0; u < SCAN; ++u) {
+                if (sv[u] != T(0)) {
+                    const int t = t0 + 64 * u + lane;
+                    s[t] = T(0);
+                    if (j0 + t != i) {
+                        T dist = ni + nj[u] - T(2) * sv[u];
+                        dist = dist > T(0) ? dist : T(0);
+#pragma unroll
+                        for (int v = 0; v < NV; ++v) {
+                            if (!((live >> v) & 1u)) continue;  // wave-uniform
+                            T c;
+                            if (gm.form[v] == 0) c = ei.p[v] * ej[u].p[v] * expm1(T(2) * gm.g[v] * sv[u]);
+                            else c = exp(-gm.g[v] * dist) - ei.p[v] * ej[u].p[v];
+                            acc[v] += (double) c * (double) pv[u].p[v];
+                        }
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        double a = acc[v];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) a += __shfl_xor(a, off);
+        if (lane == 0 && ((live >> v) & 1u)) raw[v * rstride + i] = (T) a;
+    }
+}
+
 }  // namespace
 
 // device bytes and an estimated time (s) of one on-the-fly K·p share, from the host CSR / CSC counts
@@ -632,10 +761,80 @@ void engine<T>::otf_pairs_lanes(const T *p, int64_t pstride, T *raw_out, int64_t
     }
 }
 
+// The O(m) data of the running group of gamma lanes (lanes.gam), built once per group: lane c's form — the one a fresh
+// context with its gamma chooses in setup_csr / setup_otf —, its e and q (sparse_gamma_eq: a fresh context's bits) in
+// lane_ge(c) / lane_q(c), and the lanes' e interleaved for the scan, gek[j][NV] (columns past the group: zero).
+template <typename T>
+void engine<T>::otf_gamma_group() {
+    const int nvec = (int) lanes.gam.size();
+    if (nvec < 1 || nvec > KP_MULTI_W || nvec > lanes.width) throw mi_error(-1, "bad lane count for the on-the-fly gamma lanes");
+    lanes.gform.assign((size_t) nvec, 1);
+    for (int c = 0; c < nvec; ++c) {
+        const T g = lanes.gam[(size_t) c];
+        const bool fact_ok = std::fabs((double) g) * csr.nmax <= (sizeof(T) == 8 ? 300.0 : 40.0);
+        lanes.gform[(size_t) c] = rbf_form != 1 && fact_ok ? 0 : 1;
+        sparse_gamma_eq(g, lane_ge(c), lane_q(c));
+    }
+    if (m <= 0) return;
+    auto pack = [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        hipLaunchKernelGGL((otf_pack_lanes_kernel<T, NV>), dim3((unsigned) ceil_div(m, 256)), dim3(256), 0, stream, lanes.ge.get(),
+                           lanes.vstride, nvec, m, reinterpret_cast<otf_pv<T, NV> *>(lanes.gek.get()),
+                           static_cast<const cg_scalars<T> *>(nullptr));
+        MI_LAUNCH_CHECK();
+    };
+    switch (otf_lanes_nv(nvec)) {
+        case 2: pack(std::integral_constant<int, 2>{}); break;
+        case 4: pack(std::integral_constant<int, 4>{}); break;
+        default: pack(std::integral_constant<int, KP_MULTI_W>{}); break;
+    }
+}
+
+// otf_pairs_lanes for the running group of gamma lanes: the vectors of lanes 0 .. nvec - 1 in one pass over the pairs,
+// lane l under its own rbf width (otf_kp_gammas_kernel); otf_gamma_group has run for the group
+template <typename T>
+void engine<T>::otf_pairs_gammas(const T *p, int64_t pstride, T *raw_out, int64_t rstride, int nvec, T *pk,
+                                 const cg_scalars<T> *status) {
+    if (r1 <= r0) return;
+    if (nvec < 1 || nvec > KP_MULTI_W || (size_t) nvec != lanes.gam.size() || lanes.gform.size() != lanes.gam.size())
+        throw mi_error(-1, "bad vector count for the on-the-fly gamma lanes");
+    auto launch = [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        otf_gam<T, NV> gm{};
+        for (int c = 0; c < NV; ++c) {
+            gm.g[c] = c < nvec ? lanes.gam[(size_t) c] : T(0);
+            gm.form[c] = c < nvec ? lanes.gform[(size_t) c] : 0;
+        }
+        otf_pv<T, NV> *pkv = reinterpret_cast<otf_pv<T, NV> *>(pk);
+        hipLaunchKernelGGL((otf_pack_lanes_kernel<T, NV>), dim3((unsigned) ceil_div(m, 256)), dim3(256), 0, stream, p, pstride,
+                           nvec, m, pkv, status);
+        MI_LAUNCH_CHECK();
+        hipLaunchKernelGGL((otf_kp_gammas_kernel<T, OTF_CWB, NV>), dim3((unsigned) ceil_div(r1 - r0, OTF_NT / 64)), dim3(OTF_NT),
+                           0, stream, csr.rowptr.get(), csr.col.get(), csr.val.get(), csr.ecb.get(),
+                           reinterpret_cast<const otf_jv<T> *>(csr.cjv.get()), csr.seg.get(),
+                           reinterpret_cast<const otf_ne<T> *>(csr.otf_ne.get()),
+                           reinterpret_cast<const otf_pv<T, NV> *>(lanes.gek.get()), pkv, m, csr.otf_nw, r0, r1, gm, nvec, raw_out,
+                           rstride, status);
+        MI_LAUNCH_CHECK();
+    };
+    switch (otf_lanes_nv(nvec)) {
+        case 2: launch(std::integral_constant<int, 2>{}); break;
+        case 4: launch(std::integral_constant<int, 4>{}); break;
+        default: launch(std::integral_constant<int, KP_MULTI_W>{}); break;
+    }
+}
+
 // raw += the separable part kappa_ij p_j and the diagonal, for the vector p of the lane L (the engine's own: ssc =
-// csr.ssc): sum e p (rbf) or sum p (poly) through L.red into ssc, then gram_base_kernel — O(m)
+// csr.ssc): sum e p (rbf) or sum p (poly) through L.red into ssc, then gram_base_kernel — O(m). A gamma lane's e is its
+// own (L.e), every other lane's the engine's
 template <typename T>
 void engine<T>::otf_base(const cg_lane &L, T *ssc, const T *p, const cg_scalars<T> *status) {
+    if (L.e != nullptr) {
+        launch_dot2<T>(p, L.e, nullptr, nullptr, m, L.red, status, stream);
+        launch_dot_final<T>(L.red, L.sc, FIN_PLAIN, 0, nullptr, 0, ssc, stream);
+        launch_gram_base<T>(kernel, kf(), T(0), ssc, norms.get(), L.e, p, m, L.raw, status, stream);
+        return;
+    }
     launch_dot2<T>(p, kernel == 2 ? csr.e.get() : nullptr, nullptr, nullptr, m, L.red, status, stream);
     launch_dot_final<T>(L.red, L.sc, FIN_PLAIN, 0, nullptr, 0, ssc, stream);
     T kappa = 0;
@@ -661,6 +860,8 @@ void engine<T>::otf_kp_raw(const T *p, const cg_scalars<T> *status, bool with_ba
     template void engine<T>::setup_otf(int);                                                                           \
     template void engine<T>::otf_dominant(const T *, const cg_scalars<T> *);                                           \
     template void engine<T>::otf_pairs_lanes(const T *, int64_t, T *, int64_t, int, T *, const cg_scalars<T> *);      \
+    template void engine<T>::otf_gamma_group();                                                                        \
+    template void engine<T>::otf_pairs_gammas(const T *, int64_t, T *, int64_t, int, T *, const cg_scalars<T> *);     \
     template void engine<T>::otf_base(const cg_lane &, T *, const T *, const cg_scalars<T> *);                         \
     template void engine<T>::otf_kp_raw(const T *, const cg_scalars<T> *, bool);
 INST(float)

@@ -77,6 +77,15 @@ __global__ __launch_bounds__(256) void csr_q_kernel(kfun<T> kf, const int64_t *_
     }
 }
 
+// e_i = exp(-gamma |x_i|^2) from the stored norms: csr_norms_kernel's expression, its bits (a gamma lane's e)
+template <typename T>
+__global__ __launch_bounds__(256) void csr_e_kernel(const T *__restrict__ norms, int64_t m, T gamma, T *__restrict__ e) {
+    const int64_t row = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= m) return;
+    const T v = norms[row];
+    e[row] = exp(-gamma * v);
+}
+
 // ---- CSC on the device (rows 0..m-1): a stable radix sort of the entries by column keeps the rows ascending
 // inside every column — the host counting sort's CSC (csc_host below), bit for bit ------------------------
 // entry k's row, and k itself (the sort's payload); one wave per row
@@ -1092,6 +1101,7 @@ void engine<T>::setup_csr(const int64_t *rowptr, const int32_t *col, const void 
         // kernel expansion (expand.hip) when it represents the kernel to rounding, else the Gram pattern;
         // either only within the device-memory budget, else the densified MFMA path
         csr.ex.umax = 2.0 * std::fabs((double) gamma) * amax;
+        csr.nmax = nmax;
         const bool fact_ok = kernel != 2 || std::fabs((double) gamma) * nmax <= (sizeof(T) == 8 ? 300.0 : 40.0);
         const bool elig = sparse_algo != 3 && fact_ok && expansion_eligible();
         if (sparse_algo == 2 && !elig)
@@ -1583,6 +1593,20 @@ void engine<T>::sparse_q() {
     MI_LAUNCH_CHECK();
 }
 
+// e_out = exp(-g |x_i|^2) and q_out = k_g(x_i, x_m) for the rbf width g, as norms' e and sparse_q form them on a
+// context created with gamma = g
+template <typename T>
+void engine<T>::sparse_gamma_eq(T g, T *e_out, T *q_out) {
+    if (m <= 0) return;
+    T nlast = 0;
+    for (int64_t k = 0; k < d; ++k) nlast = std::fma(xlast_h[k], xlast_h[k], nlast);
+    hipLaunchKernelGGL(csr_e_kernel<T>, dim3((unsigned) ceil_div(m, 256)), dim3(256), 0, stream, norms.get(), m, g, e_out);
+    MI_LAUNCH_CHECK();
+    hipLaunchKernelGGL(csr_q_kernel<T>, dim3((unsigned) ceil_div(m, 16)), dim3(256), 0, stream, kfun<T>{ kernel, degree, g, coef0 },
+                       csr.rowptr.get(), csr.col.get(), csr.rvals(), m, xlast.get(), nlast, norms.get(), q_out);
+    MI_LAUNCH_CHECK();
+}
+
 template <typename T>
 void engine<T>::sparse_kp_raw(const T *p, const cg_scalars<T> *status, bool with_base) {
     if (factored()) {
@@ -1681,6 +1705,7 @@ void launch_gram_base(int kernel, kfun<T> kf, T kappa, const T *ssc, const T *no
     template void engine<T>::setup_csr(const int64_t *, const int32_t *, const void *, int, int64_t, int64_t); \
     template void engine<T>::build_gram_blocks(const int64_t *, int64_t);                                     \
     template void engine<T>::sparse_q();                                                                      \
+    template void engine<T>::sparse_gamma_eq(T, T *, T *);                                                    \
     template void engine<T>::sparse_kp_raw(const T *, const cg_scalars<T> *, bool);                           \
     template void engine<T>::sparse_dominant(const T *, const cg_scalars<T> *);                               \
     template void engine<T>::spmv_pass_csc(const T *, const cg_scalars<T> *);                                 \

@@ -104,6 +104,7 @@ struct csr_data {
     spmv_plan<T> spmv_csc, spmv_csr;
     rb_plan<T> rb_csr;  // one GPU: the CSR pass as row blocks with the CG finalize fused (spmv.hpp)
     dev_buf<T> e;                     // rbf separable factor exp(-gamma n_i)
+    double nmax = 0.0;                // the largest |x_i|^2 of rows 0..m-1 (the factored rbf form's range check)
 
     // Gram pattern
     bool have_gram = false;
