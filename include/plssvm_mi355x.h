@@ -388,6 +388,22 @@ PLSSVM_MI_API int plssvm_mi_kp_gammas(plssvm_mi_ctx *ctx, const double *gammas, 
 PLSSVM_MI_API int plssvm_mi_learn_gammas(plssvm_mi_ctx *ctx, const void *y, const double *gammas, const double *costs,
                                          int64_t nlane, int64_t imax, double eps, void *alpha_out, double *bias_out,
                                          double *delta_trace, int64_t *iters);
+/* plssvm_mi_predict_gammas_dense: the decision values of the nlane models (gammas[l], ALPHA + l * lda, bias[l]) on the
+ * context's n points (e.g. what plssvm_mi_learn_gammas returned) for the np dense points Z[np][d], OUT[nlane][ldo],
+ * in one call: the points are uploaded, centred and transposed once, and groups of up to 8 lanes share each pass
+ * over the pair distances, which are formed once per 128 x 128 tile and stay in registers while every lane applies
+ * its own exp(-gamma_l dist) and alpha_l. Row l is BITWISE plssvm_mi_predict_dense with
+ * (alpha_l, bias[l]) on a fresh context created with gamma = gammas[l] on the same data, whatever nlane, the lane's
+ * position, np, the points' order, the chunking (PLSSVM_MI_PRED_CHUNK) or the run; lanes equal in gamma are not merged.
+ * plssvm_mi_info.predict_algo reports PLSSVM_MI_PREDICT_TILES, plssvm_mi_get_predict_stats {min(nlane, 8), 1}; the
+ * context's own gamma, cost, q, weights and stored tiles are untouched.
+ * Offered for dense data (plssvm_mi_setup_dense) with PLSSVM_MI_KERNEL_RBF or _LAPLACIAN on one GPU. Sparse contexts,
+ * the linear or polynomial kernel, a group, a simulated rank: PLSSVM_MI_ERR_UNSUPPORTED, plssvm_mi_last_error names
+ * the reason ("gamma lanes run on ..."), the context stays usable. nlane < 1, a gamma that is not finite and > 0,
+ * lda < n, ldo < np, d != the context's d, a null pointer: PLSSVM_MI_ERR_ARG. np == 0: OK, OUT untouched. */
+PLSSVM_MI_API int plssvm_mi_predict_gammas_dense(plssvm_mi_ctx *ctx, const double *gammas, const void *ALPHA, int64_t nlane,
+                                                 int64_t lda, const double *bias, const void *Z, int64_t np, int64_t d,
+                                                 void *OUT, int64_t ldo);
 /* Timing hook: plssvm_mi_time_kp's K·p time for the product with nrhs resident vectors (in groups of the width; one at
  * a time where nothing is batched), averaged over `reps` products, measured with hipEvents on the context's stream. */
 PLSSVM_MI_API int plssvm_mi_time_kp_multi(plssvm_mi_ctx *ctx, int64_t nrhs, int reps, double *ms_per_kp);

@@ -635,6 +635,37 @@ class CSVM:
             self.costs = cc
         return self
 
+    def predict_values_gammas(self, points, gammas=None, alphas=None, biases=None):
+        """Decision values [np][K] of the K models (gammas[k], alphas[k], biases[k]) (defaults: what learn_gammas left in
+        gammas, alphas, biases) for dense points [np][d] in one call (plssvm_mi_predict_gammas_dense): the points are
+        prepared once and up to 8 widths share each pass over the pair distances. Column k is bitwise predict_values
+        with (alphas[k], biases[k]) of a fresh context with gamma = gammas[k]. Dense data, rbf or laplacian, one GPU;
+        other setups raise BackendError with the reason. The context's own gamma and stored tiles stay."""
+        gammas = getattr(self, "gammas", None) if gammas is None else gammas
+        alphas = self.alphas if alphas is None else alphas
+        biases = self.biases if biases is None else biases
+        if gammas is None or alphas is None:
+            raise ValueError("No gammas or alphas provided for prediction!")
+        g = self._gammas(gammas)
+        A = _rows(alphas, self.dtype, self.num_data_points, "alphas")
+        K, lda = A.shape
+        b = np.zeros(K, dtype=np.float64) if biases is None else np.ascontiguousarray(np.atleast_1d(biases), dtype=np.float64)
+        if g.shape != (K,) or b.shape != (K,):
+            raise ValueError(f"gammas and biases must have {K} entries, one per row of alphas")
+        Z = np.ascontiguousarray(points, dtype=self.dtype)
+        if Z.ndim != 2:
+            raise ValueError("points must be a 2-D array [np][d]")
+        if not self._on_device:
+            self.setup_data_on_device()
+        out = np.zeros((K, max(Z.shape[0], 1)), dtype=self.dtype)
+        self._check(_abi.lib().plssvm_mi_predict_gammas_dense(self._ctx, _ptr(g), _ptr(A), K, lda, _ptr(b), _ptr(Z), Z.shape[0],
+                                                              Z.shape[1], _ptr(out), out.shape[1]))
+        return np.ascontiguousarray(out[:, : Z.shape[0]].T)
+
+    def predict_gammas(self, points):
+        """Predicted labels (+-1) [np][K] of the learn_gammas models; a value of exactly 0 is negative, as in predict()."""
+        return np.where(self.predict_values_gammas(points) > 0, self.dtype.type(1), self.dtype.type(-1))
+
     def train_values(self, alphas=None, biases=None):
         """Decision values [n][K] of K models (default: alphas, biases as the last multi-lane learn left them) on the
         context's own n points, held-out ones included, from the kernel matrix the context already holds

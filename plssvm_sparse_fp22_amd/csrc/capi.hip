@@ -433,6 +433,17 @@ int plssvm_mi_learn_gammas(plssvm_mi_ctx *ctx, const void *y, const double *gamm
     });
 }
 
+int plssvm_mi_predict_gammas_dense(plssvm_mi_ctx *ctx, const double *gammas, const void *ALPHA, int64_t nlane, int64_t lda,
+                                   const double *bias, const void *Z, int64_t np, int64_t d, void *OUT, int64_t ldo) {
+    if (!ctx || !gammas || !ALPHA || !bias || nlane < 1) return PLSSVM_MI_ERR_ARG;
+    return ctx->call([&](auto &e) {
+        using T = std::remove_reference_t<decltype(e.gamma)>;
+        std::vector<T> b(bias, bias + nlane);
+        e.predict_gammas(gammas, static_cast<const T *>(ALPHA), nlane, lda, b.data(), static_cast<const T *>(Z), np, d,
+                         static_cast<T *>(OUT), ldo);
+    });
+}
+
 int plssvm_mi_time_kp_multi(plssvm_mi_ctx *ctx, int64_t nrhs, int reps, double *ms_per_kp) {
     if (!ctx || nrhs < 1) return PLSSVM_MI_ERR_ARG;
     return ctx->call([&](auto &e) { e.time_kp_multi(nrhs, reps, ms_per_kp); });

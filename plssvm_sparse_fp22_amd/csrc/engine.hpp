@@ -557,6 +557,27 @@ struct engine : engine_base {
                        const int32_t *zcol, const void *zval, int zfmt, int64_t np, T *out, int64_t ldo);
     void predict_shared(const T *alpha_host, int64_t nclass, int64_t lda, const T *bias, const T *Z, const int64_t *zrowptr,
                         const int32_t *zcol, const void *zval, int zfmt, int64_t np, T *out, int64_t ldo);
+    // What predict_tiles and predict_gammas share: the model upload, the chunking of the points, their centring shift,
+    // transpose and norms, and the download. pass(g) launches the tile and finish kernels of one group of up to
+    // KP_MULTI_W models (rows c0 .. c0 + nc of the nall) on one prepared chunk of points.
+    struct tile_pass {
+        int64_t c0;                 // the group's first model
+        int nc, nall;               // models in the group, models in the call
+        const T *A, *ab;            // the group's alpha rows [nc][n_pad]; ab + c0 of [alpha_m x nall | bias x nall]
+        const T *ZT, *znorms;       // the chunk's points [d_pad][np_pad] and their squared norms (rbf)
+        int64_t np_pad, npoints, nseg;
+        T nlast;                    // |x_m|^2
+        T *part, *out;              // [nc][nseg][np_pad] scratch; the group's rows of the chunk's output [nall][np_pad]
+    };
+    template <typename PASS>
+    void predict_tiles_run(const T *alpha_host, int64_t nclass, int64_t lda, const T *bias, const T *Z, const int64_t *zrowptr,
+                           const int32_t *zcol, const void *zval, int zfmt, int64_t np, T *out, int64_t ldo, PASS &&pass);
+    // Gamma lanes of predict (predict_gamma.hip): lane l is the model (gammas[l], alpha_l, bias_l) on
+    // the context's support vectors, out[l] bitwise what a context created with gammas[l] predicts with (alpha_l,
+    // bias_l). Dense data with the rbf or laplacian kernel on one GPU; groups of up to KP_MULTI_W lanes share each pass
+    // over the pair distances. The engine's gamma, cost, q, weights and stored tiles are not touched.
+    void predict_gammas(const double *gammas, const T *alpha_host, int64_t nlane, int64_t lda, const T *bias, const T *Z,
+                        int64_t np, int64_t dz, T *out, int64_t ldo);
     // plssvm_mi_get_predict_stats: classes per pass over the support vectors and point uploads of the last predict call
     int64_t predict_classes_per_pass = 0, predict_uploads = 0;
     int predict_algo = 0;  // PLSSVM_MI_PREDICT_*: the path of the last predict call

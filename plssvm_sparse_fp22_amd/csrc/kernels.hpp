@@ -195,6 +195,19 @@ void launch_predict_finish(kfun<T> kf, const T *part, int64_t nseg, const T *ZT,
                            int64_t d, const T *xlast, T nlast, const T *ab, int ncls, int nclass, int64_t np, T *out,
                            hipStream_t s);
 
+// Gamma lanes of the two (predict_gamma.hip; rbf and laplacian, kf.gamma is not read): lane l < nlane
+// <= KP_MULTI_W has the width gammas[l] (host values) and the coefficients A + l * n_pad. A tile's distances are formed
+// once and every lane's kernel values come from them in registers: part[l] / out[l] are bitwise what the two launches
+// above give for A_l with kf.gamma = gammas[l].
+template <typename T>
+void launch_predict_tiles_gamma(kfun<T> kf, const T *gammas, const T *XT, const T *norms, int64_t n_pad, int64_t nb,
+                                int64_t d_pad, const T *ZT, const T *znorms, int64_t np_pad, int64_t npoints, const T *A,
+                                int nlane, T *part, hipStream_t s);
+template <typename T>
+void launch_predict_finish_gamma(kfun<T> kf, const T *gammas, const T *part, int64_t nseg, const T *ZT, const T *znorms,
+                                 int64_t np_pad, int64_t d, const T *xlast, T nlast, const T *ab, int nlane, int nall,
+                                 int64_t np, T *out, hipStream_t s);
+
 // raw[i] = sum over the column blocks c in order of row i's slab values of the tiles whose super-block lies
 // in [s0, s1) (tile (Ib, c) row sums for c <= Ib, tile (c, Ib) column sums for c > Ib); i < m
 template <typename T>

@@ -1,4 +1,4 @@
-// Device helpers shared by the MFMA tile kernels (kp_tiles.hip, kp_gamma.hip, predict_tiles.hip): the kernel function on an
+// Device helpers shared by the MFMA tile kernels (kp_tiles.hip, kp_gamma.hip, predict_tiles.hip, predict_gamma.hip): the kernel function on an
 // accumulator value, the table-driven fp64 exp of the RBF epilogue and the global -> LDS DMA of the K loop.
 #pragma once
 
@@ -201,6 +201,22 @@ template <typename T>
 __device__ __forceinline__ void kp_slab_store(T *at, T v) {
     if constexpr (KP_SLAB_NT != 0) __builtin_nontemporal_store(v, at);
     else *at = v;
+}
+
+// ---- shared by the gamma-lane kernels of kp_gamma.hip and predict_gamma.hip ----
+// the lanes' gammas, by value in the kernel arguments: LW = 1, 2, 4, 8 slots (the instance of the smallest LW >= the
+// lane count is launched)
+template <typename T, int LW>
+struct kp_gammas {
+    T g[LW];
+};
+// gam.g[c] for a wave-uniform c without indexing the argument struct by a register: a chain of scalar selects
+template <typename T, int LW>
+__device__ __forceinline__ T kp_gamma_at(const kp_gammas<T, LW> &gam, int c) {
+    T g = gam.g[0];
+#pragma unroll
+    for (int l = 1; l < LW; ++l) g = c == l ? gam.g[l] : g;
+    return g;
 }
 
 // LDS layout of the epilogue's reduction buffers (element counts): p_I, p_J, n_I, n_J, then row partials

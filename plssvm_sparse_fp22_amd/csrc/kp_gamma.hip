@@ -23,21 +23,8 @@ namespace plssvm_mi {
 
 namespace {
 
-// the lanes' gammas, by value in the kernel arguments: LW = 1, 2, 4, 8 slots (the instance of the smallest LW >= the
-// lane count is launched; LW = 1 has no lane loop and no stop-flag mask)
-template <typename T, int LW>
-struct kp_gammas {
-    T g[LW];
-};
-// gam.g[c] for a wave-uniform c without indexing the argument struct by a register: a chain of scalar selects
-template <typename T, int LW>
-__device__ __forceinline__ T kp_gamma_at(const kp_gammas<T, LW> &gam, int c) {
-    T g = gam.g[0];
-#pragma unroll
-    for (int l = 1; l < LW; ++l) g = c == l ? gam.g[l] : g;
-    return g;
-}
-
+// (kp_gammas / kp_gamma_at, the lanes' gammas in the kernel arguments: kp_device.hpp; LW = 1 has no lane loop and no
+// stop-flag mask)
 template <typename T>
 constexpr int kpg_waves() { return sizeof(T) == 8 ? 2 : 3; }
 

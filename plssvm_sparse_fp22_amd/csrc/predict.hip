@@ -495,9 +495,10 @@ void engine<T>::predict_shared(const T *alpha_host, int64_t nclass, int64_t lda,
 // straight from the caller's row-major buffer (CSR points: densified per chunk on the host), are transposed to
 // ZT[d_pad][chunk] on the device, and each chunk's decision values come back per class row.
 template <typename T>
-void engine<T>::predict_tiles(const T *alpha_host, int64_t nclass, int64_t lda, const T *bias, const T *Z,
-                              const int64_t *zrowptr, const int32_t *zcol, const void *zval, int zfmt, int64_t np, T *out,
-                              int64_t ldo) {
+template <typename PASS>
+void engine<T>::predict_tiles_run(const T *alpha_host, int64_t nclass, int64_t lda, const T *bias, const T *Z,
+                                  const int64_t *zrowptr, const int32_t *zcol, const void *zval, int zfmt, int64_t np, T *out,
+                                  int64_t ldo, PASS &&pass) {
     MI_HIP_CHECK(hipSetDevice(device));
     predict_algo = PLSSVM_MI_PREDICT_TILES;
     const int ncp = (int) std::min<int64_t>(nclass, KP_MULTI_W);  // classes per pass
@@ -559,15 +560,64 @@ void engine<T>::predict_tiles(const T *alpha_host, int64_t nclass, int64_t lda, 
         if (kernel == 2) launch_row_norms<T>(ztd.get(), pcp, d, nzd.get(), stream);
         for (int64_t c0 = 0; c0 < nclass; c0 += ncp) {
             const int nc = (int) std::min<int64_t>(ncp, nclass - c0);
-            launch_predict_tiles<T>(kf(), XT.get(), norms.get(), n_pad, nb, d_pad, ztd.get(), nzd.get(), pcp, c,
-                                    A.get() + c0 * n_pad, nc, pd.get(), stream);
-            launch_predict_finish<T>(kf(), pd.get(), nseg, ztd.get(), nzd.get(), pcp, d, xlast.get(), nlast, ab.get() + c0,
-                                     nc, (int) nclass, c, od.get() + c0 * pcp, stream);
+            pass(tile_pass{ c0, nc, (int) nclass, A.get() + c0 * n_pad, ab.get() + c0, ztd.get(), nzd.get(), pcp, c, nseg, nlast,
+                            pd.get(), od.get() + c0 * pcp });
         }
         for (int64_t k = 0; k < nclass; ++k)
             MI_HIP_CHECK(hipMemcpyAsync(out + k * ldo + p0, od.get() + k * pcp, sizeof(T) * (size_t) c, hipMemcpyDeviceToHost, stream));
         MI_HIP_CHECK(hipStreamSynchronize(stream));
     }
+}
+
+template <typename T>
+void engine<T>::predict_tiles(const T *alpha_host, int64_t nclass, int64_t lda, const T *bias, const T *Z,
+                              const int64_t *zrowptr, const int32_t *zcol, const void *zval, int zfmt, int64_t np, T *out,
+                              int64_t ldo) {
+    predict_tiles_run(alpha_host, nclass, lda, bias, Z, zrowptr, zcol, zval, zfmt, np, out, ldo, [&](const tile_pass &g) {
+        launch_predict_tiles<T>(kf(), XT.get(), norms.get(), n_pad, nb, d_pad, g.ZT, g.znorms, g.np_pad, g.npoints, g.A, g.nc,
+                                g.part, stream);
+        launch_predict_finish<T>(kf(), g.part, g.nseg, g.ZT, g.znorms, g.np_pad, d, xlast.get(), g.nlast, g.ab, g.nc, g.nall,
+                                 g.npoints, g.out, stream);
+    });
+}
+
+// Gamma lanes (engine.hpp): the checks, then predict_tiles' preparation with the gamma kernels per group of lanes
+template <typename T>
+void engine<T>::predict_gammas(const double *gammas, const T *alpha_host, int64_t nlane, int64_t lda, const T *bias, const T *Z,
+                               int64_t np, int64_t dz, T *out, int64_t ldo) {
+    need_data();
+    if (gammas == nullptr || nlane < 1) throw mi_error(-1, "at least one gamma is needed");
+    std::vector<T> gam((size_t) nlane);  // rounded to T as plssvm_mi_create rounds a context's gamma
+    for (int64_t k = 0; k < nlane; ++k) {
+        gam[(size_t) k] = (T) gammas[k];
+        if (!(gammas[k] > 0) || !std::isfinite(gammas[k]) || !(gam[(size_t) k] > T(0)) || !std::isfinite(gam[(size_t) k]))
+            throw mi_error(-1, "gamma " + std::to_string(k) + " is not a finite number > 0");
+    }
+    const char *why = (kernel != 2 && kernel != KF_LAPLACIAN) ? "a kernel without a distance that all gammas share (linear, polynomial)"
+                      : sparse                                ? "sparse (CSR) data"
+                      : (sim_world > 0)                       ? "a simulated rank"
+                      : (world > 1 || comm != nullptr || xchg != nullptr || shard) ? "a multi-GPU group"
+                                                              : nullptr;
+    if (why != nullptr)
+        throw mi_error(-5, std::string("gamma lanes run on dense data with the rbf or laplacian kernel on one GPU when they "
+                                       "predict; this context is ") + why + " (use one context per gamma instead)");
+    if (np == 0) return;
+    if (np < 0 || Z == nullptr) throw mi_error(-1, "no points to predict");
+    if (dz != d)
+        throw mi_error(-1, "Number of features per data point (" + std::to_string(d) +
+                               ") must match the number of features per predict point (" + std::to_string(dz) + ")!");
+    if (alpha_host == nullptr) throw mi_error(-1, "No alphas provided for prediction!");
+    if (bias == nullptr) throw mi_error(-1, "no biases");
+    if (out == nullptr) throw mi_error(-1, "no output buffer");
+    if (lda < n || ldo < np) throw mi_error(-1, "leading dimension too small");
+    predict_tiles_run(alpha_host, nlane, lda, bias, Z, nullptr, nullptr, nullptr, PLSSVM_MI_VAL_REAL, np, out, ldo,
+                      [&](const tile_pass &g) {
+                          const T *gl = gam.data() + g.c0;
+                          launch_predict_tiles_gamma<T>(kf(), gl, XT.get(), norms.get(), n_pad, nb, d_pad, g.ZT, g.znorms, g.np_pad,
+                                                        g.npoints, g.A, g.nc, g.part, stream);
+                          launch_predict_finish_gamma<T>(kf(), gl, g.part, g.nseg, g.ZT, g.znorms, g.np_pad, d, xlast.get(), g.nlast,
+                                                         g.ab, g.nc, g.nall, g.npoints, g.out, stream);
+                      });
 }
 
 // gpu_csvm::predict (src/plssvm/backends/gpu_csvm.cpp:52-120) for nclass models on the same support vectors:
@@ -624,7 +674,9 @@ void engine<T>::predict(const T *alpha_host, T bias, const T *Z, const int64_t *
     template void engine<T>::predict(const T *, T, const T *, const int64_t *, const int32_t *, const void *, int, \
                                      int64_t, int64_t, T *);                                                    \
     template void engine<T>::predict_multi(const T *, int64_t, int64_t, const T *, const T *, const int64_t *,  \
-                                           const int32_t *, const void *, int, int64_t, int64_t, T *, int64_t);
+                                           const int32_t *, const void *, int, int64_t, int64_t, T *, int64_t); \
+    template void engine<T>::predict_gammas(const double *, const T *, int64_t, int64_t, const T *, const T *, int64_t, \
+                                            int64_t, T *, int64_t);
 INST(float)
 INST(double)
 #undef INST
